@@ -11,6 +11,9 @@ the data path: records are independent).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+`--dump-outputs DIR` also writes what the last timed step returned (counts, a seeded sample of records' token ids) as
+DIR/*.npy, for comparing two builds output for output (dump_encode_outputs).
+
 Rank 0 prints ONE JSON line.  `value` = token ids produced per second by the whole job
 (inputs already resident in HBM).  `roofline` prices the timed kernels against HBM with the
 algorithmic bytes of SURVEY.md §8d: 8*12*L read + 4*T written per record.  `cpu_baseline` times
@@ -848,6 +851,35 @@ def bench_train(args, tk, vocab, merges, pc, world, rank, dev, x_host, loader_di
     return out
 
 
+DUMP_IDS_BUDGET = 60 << 20     # bytes of DIR/ids.npy at most (the whole dump stays under 64 MB)
+
+
+def dump_encode_outputs(out_dir, ids, counts, max_rows=256):
+    """What the timed step hands its caller, the (ids, counts) pair of quantize_encode, as float32 .npy files in `out_dir`:
+    counts.npy   (B,)    the number of token ids of every record;
+    ids_rows.npy (R,)    a fixed sample of R records (seed 0, sorted), the same for every run with the same --batch / --L;
+    ids.npy      (R, W)  those records' token ids, W = the sample's largest count, -1 past each record's own count (the buffer
+                         there holds nothing the call defined).
+    Ids and counts are below 2**24, so float32 holds them exactly.  R = min(B, max_rows, what fits DUMP_IDS_BUDGET at W = 12 L)."""
+    import torch
+    B, n = ids.shape
+    rows_fit = DUMP_IDS_BUDGET // (4 * n)
+    assert rows_fit >= 1, f"one record of {n} token slots is over the dump budget"
+    R = min(B, max_rows, rows_fit)
+    rows = np.sort(np.random.default_rng(0).choice(B, size=R, replace=False))
+    c = counts.cpu().numpy().astype(np.int64)
+    W = int(c[rows].max())
+    sel = ids.index_select(0, torch.from_numpy(rows).to(ids.device))[:, :W].cpu().numpy()
+    out = np.full((R, W), -1.0, dtype=np.float32)
+    for i, r in enumerate(rows):
+        out[i, : c[r]] = sel[i, : c[r]]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "counts.npy"), c.astype(np.float32))
+    np.save(os.path.join(out_dir, "ids_rows.npy"), rows.astype(np.float32))
+    np.save(os.path.join(out_dir, "ids.npy"), out)
+    sys.stderr.write(f"bench.py: outputs of the last timed step in {out_dir}: counts ({B},), ids ({R}, {W}) of records ids_rows\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -858,15 +890,19 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the train-step part (encode metric only)")
     ap.add_argument("--train-batch", type=int, default=32, help="samples per GPU per train step")
-    ap.add_argument("--train-steps", type=int, default=10, help="timed steps of every train leg (the boxes differ by 1-2 %: ten steps per figure, not two or three)")
+    ap.add_argument("--train-steps", type=int, default=10, help="timed steps of every train leg (the boxes differ by 1-2 %%: ten steps per figure, not two or three)")
     ap.add_argument("--full-logits", action="store_true", help="loss head over every row, as the reference materialises it")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 object (Gemma-2B dims LoRA step + generate)")
     ap.add_argument("--no-c1", action="store_true", help="skip the C1 object (12x1000 records + GPT-2-small forward, batch 4)")
     ap.add_argument("--no-lora-leg", action="store_true", help="full fine-tune leg only (profiling: one mode per kernel trace)")
-    ap.add_argument("--overlap-optimizer", action="store_true", help="train legs: parameter updates on a side stream under the next forward (A/B; measured +0.4 %)")
+    ap.add_argument("--overlap-optimizer", action="store_true", help="train legs: parameter updates on a side stream under the next forward (A/B; measured +0.4 %%)")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra objects of the line (batch sweep, tokenizer trainer, offline conditioning, full-logits leg)")
     ap.add_argument("--lora", action="store_true", help="train LoRA adapters (r16, alpha 32, dropout 0.05; frozen base) as the reference's script does")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's records) as DIR/*.npy: see dump_encode_outputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # --gpus N must be what the launcher started: checked before anything is generated or initialised (exit 2, no line); the process group's own size is checked again below
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
         sys.stderr.write(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={os.environ.get('WORLD_SIZE', '1')}: start it as python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus}\n")
@@ -966,6 +1002,8 @@ def main():
     wall = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1) / args.steps
     tokens_rank = int(counts.sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_encode_outputs(args.dump_outputs, ids, counts)
 
     if world > 1:
         t = torch.tensor([wall], dtype=torch.float64, device=dev)

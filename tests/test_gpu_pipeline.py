@@ -250,3 +250,36 @@ def test_bench_line_contract_single_gpu():
     c = out["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["unit"] == "tokens/s" and c["value"] > 0 and "records" in c["sample"]
     assert c["quantiser_python_style_symbols_per_s"] < c["quantiser_c_symbols_per_s"]
+
+
+def test_bench_dump_outputs_are_the_oracle_ids():
+    """bench.py --dump-outputs writes what the last timed step returned: every record's count and the sampled records' ids,
+    each equal to the CPU oracle's parse of the same seeded record."""
+    import subprocess
+    import sys
+    import tempfile
+    from ecg_byte_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    env["ECGB_BENCH_WORKERS"] = "1"
+    with tempfile.TemporaryDirectory() as d:
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "300", "--L", "1000",
+                              "--no-train", "--no-c1", "--no-extras", "--no-cpu-baseline", "--dump-outputs", d],
+                             cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        z = {k: np.load(os.path.join(d, f"{k}.npy")) for k in ("counts", "ids_rows", "ids")}
+    assert all(v.dtype == np.float32 for v in z.values())
+    assert abs(z["counts"].sum() - out["tokens_per_record"] * 300) <= 1e-5 * z["counts"].sum()     # (the line carries six significant digits)
+    _, merges, pc = load_tokenizer("c1")
+    trie = O.Trie(merges)
+    x = synth.synth_ecg(300, 1000, seed=0)
+    rows = z["ids_rows"].astype(np.int64)
+    assert rows.size == 256
+    for i, r in enumerate(rows):
+        ref = trie.quantize_encode(x[r], pc["percentile_1"], pc["percentile_99"])
+        assert z["counts"][r] == ref.size
+        assert np.array_equal(z["ids"][i, : ref.size].astype(np.uint32), ref) and np.all(z["ids"][i, ref.size:] == -1), f"record {r}"

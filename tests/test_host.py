@@ -380,3 +380,31 @@ def test_four_wave_gemm_refuses_operands_its_32_bit_dma_offsets_cannot_span(lib)
     assert ok(1, 1 << 26, 2048, 4096) == 0          # NN's A is a row operand: 63 rows of 2^27 bytes
     assert ok(0, 2048, 2048, 1 << 31) == 0          # NT: the contraction itself runs along the row
     assert ok(0, 0, 2048, 64) == 0
+
+
+def test_bench_dump_outputs_sample_and_budget(tmp_path):
+    """bench.py --dump-outputs: every record's count, a seeded sample of records' ids cut at their counts (-1 past them),
+    the same sample on every call, float32 only, and the ids under the budget however long a record is."""
+    import torch
+    import bench
+    B, n = 300, 40
+    rng = np.random.default_rng(7)
+    counts = torch.from_numpy(rng.integers(1, n + 1, size=B).astype(np.int32))
+    ids = torch.from_numpy(rng.integers(0, 5000, size=(B, n)).astype(np.int32))
+    bench.dump_encode_outputs(str(tmp_path / "a"), ids, counts)
+    bench.dump_encode_outputs(str(tmp_path / "b"), ids, counts)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("counts", "ids_rows", "ids")}
+    for k, v in got.items():
+        assert v.dtype == np.float32 and np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")), k
+    assert np.array_equal(got["counts"], counts.numpy())
+    rows = got["ids_rows"].astype(np.int64)
+    assert rows.size == 256 and np.all(np.diff(rows) > 0) and rows[-1] < B
+    c = counts.numpy()[rows]
+    assert got["ids"].shape == (256, c.max())
+    for i, r in enumerate(rows):
+        assert np.array_equal(got["ids"][i, : c[i]], ids.numpy()[r, : c[i]]) and np.all(got["ids"][i, c[i]:] == -1)
+    # rows of 12 x 500 000 slots: the sample shrinks to what fits the budget
+    wide = torch.zeros((1, 6_000_000), dtype=torch.int32).expand(64, -1)
+    bench.dump_encode_outputs(str(tmp_path / "w"), wide, torch.full((64,), 6_000_000, dtype=torch.int32))
+    assert os.path.getsize(tmp_path / "w" / "ids.npy") <= bench.DUMP_IDS_BUDGET + 4096
+    assert sum(os.path.getsize(tmp_path / "w" / f) for f in os.listdir(tmp_path / "w")) < 64 << 20
