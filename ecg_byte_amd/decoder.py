@@ -227,10 +227,39 @@ class _LossFn(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
+class _AttnSink:
+    """output_attentions of one forward, filled layer by layer by _hidden_states(attn_out=...): each layer hands over its fused qkv buffer, the key
+    mask and the row log-sum-exps ops.attn_fwd returned, and ops.attn_probs forms the probabilities -- every layer's bf16 [B, Hq, S, S] (full form), or
+    their mean over layers and heads added into one fp32 [B, S, S] (mean form: weight 1 / (L * Hq), accumulating from layer 1 on)."""
+
+    def __init__(self, n_layers, Hq, Hkv, D, mean):
+        self.n_layers, self.Hq, self.Hkv, self.D, self.mean = n_layers, Hq, Hkv, D, mean
+        self.layers, self.psum = [], None
+
+    def __call__(self, i, qkv, mask, lse, B, S):
+        Hq, Hkv, D = self.Hq, self.Hkv, self.D
+        scale = 1.0 / math.sqrt(D)
+        if self.mean:
+            if self.psum is None:
+                self.psum = torch.empty((B, S, S), dtype=torch.float32, device=qkv.device)
+            ops.attn_probs(qkv, mask, lse, B, S, Hq, Hkv, D, scale, psum=self.psum, weight=1.0 / (self.n_layers * Hq), accumulate=i > 0)
+        else:
+            probs = torch.empty((B, Hq, S, S), dtype=torch.bfloat16, device=qkv.device)
+            ops.attn_probs(qkv, mask, lse, B, S, Hq, Hkv, D, scale, probs=probs)
+            self.layers.append(probs)
+
+    def result(self):
+        if self.mean:
+            B, S = self.psum.shape[0], self.psum.shape[1]
+            return (self.psum.view(B, 1, S, S),)
+        return tuple(self.layers)
+
+
 class HipCausalLM(nn.Module):
     # HipAdam(overlap=True) needs the forward to wait per parameter group (`_wait_group`) and backward / inference to `sync_optimizer`: a subclass whose
     # own forward / backward do not (HipGPT2LM) sets this False and gets the plain in-stream step
     supports_optimizer_overlap = True
+    output_attentions_built = True   # forward(output_attentions=...) served by _hidden_states(attn_out=...); a subclass with its own _hidden_states sets False
     decode_attn_one = True      # a decode step's RoPE + append + attention as one launch where the shape allows (ops.decode_one_ok); False: round 4's four launches, the same bits
     decode_lora_one = False     # True: a decode step's o / down adapter sites form t = scale * x A^T inside the projection's launch (ops.gemm_nt_lora_decode: two launches a layer less, the same
                                 # bits) -- measured 503 against 508 tokens/s at the C5 shape: two dependent dot products and a hand-over between XCDs take what the launch boundary took
@@ -352,17 +381,44 @@ class HipCausalLM(nn.Module):
                   os.path.join(path, "model.safetensors"), metadata={"format": "pt"})
 
     def forward(self, input_ids=None, attention_mask=None, labels=None, position_ids=None, output_attentions=False, **_):
+        """HF's causal-LM forward: logits (labels None), or the loss.  output_attentions, on the two no-grad paths (logits forward; validation loss with
+        grad disabled):
+          False -- attentions None;
+          True  -- a tuple of num_hidden_layers bf16 tensors [B, Hq, S, S] (HF's eager layout; rows with no visible key hold 1/S);
+          "mean" -- a 1-tuple holding one fp32 [B, 1, S, S], the mean over layers and query heads (what the reference's interpreter forms from the tuple).
+        A grad-enabled forward (the training step) returns attentions None whatever is asked.  The probabilities come from ecgb_attn_probs (fused
+        attention, head_dim 64 / 128 / 256); the materialised path raises NotImplementedError when they are asked for."""
         if labels is None:   # inference forward: logits only (no autograd graph)
             with torch.no_grad():
                 B, S = input_ids.shape
-                hf = self._hidden_states(input_ids, attention_mask, position_ids)
+                sink = self._attn_sink(output_attentions)
+                hf = self._hidden(input_ids, attention_mask, position_ids, sink)
                 logits = ops.gemm_nt(hf, self.embed.data)[:, :self.cfg.vocab_size].float().view(B, S, -1)
-            return SimpleNamespace(loss=None, logits=logits, attentions=None)
+            return SimpleNamespace(loss=None, logits=logits, attentions=sink.result() if sink else None)
         if not torch.is_grad_enabled():   # validation: loss only, nothing kept for a backward
-            return SimpleNamespace(loss=self._eval_loss(input_ids, attention_mask, labels, position_ids), logits=None, attentions=None)
+            sink = self._attn_sink(output_attentions)
+            loss = self._eval_loss(input_ids, attention_mask, labels, position_ids, attn_out=sink)
+            return SimpleNamespace(loss=loss, logits=None, attentions=sink.result() if sink else None)
         anchor = self._anchor   # a parameter that requires grad, so autograd records the node
         loss = _LossFn.apply(anchor, self, input_ids, attention_mask, labels, position_ids)
         return SimpleNamespace(loss=loss, logits=None, attentions=None)
+
+    def _attn_sink(self, output_attentions):
+        """The per-layer collector of output_attentions (None when they are not asked for)."""
+        if not output_attentions:
+            return None
+        if output_attentions is not True and output_attentions != "mean":
+            raise ValueError(f"output_attentions={output_attentions!r}: False, True or 'mean'")
+        if not self.output_attentions_built or not self.fused_attention:
+            raise NotImplementedError(f"output_attentions: built for the fused attention path (head_dim in {ops.FUSED_HEAD_DIMS}, Llama / Gemma blocks); "
+                                      f"this model (head_dim {self.cfg.head_dim}, {type(self).__name__}) does not provide them")
+        c = self.cfg
+        return _AttnSink(c.num_hidden_layers, c.num_attention_heads, c.num_key_value_heads, c.head_dim, output_attentions == "mean")
+
+    def _hidden(self, input_ids, attention_mask, position_ids, sink):
+        if sink is None:
+            return self._hidden_states(input_ids, attention_mask, position_ids)
+        return self._hidden_states(input_ids, attention_mask, position_ids, attn_out=sink)
 
     def resize_token_embeddings(self, n: int):
         """transformers/modeling_utils.py:2080-2176, with new rows drawn as modeling_utils.py:2464-2489 does:
@@ -860,10 +916,13 @@ class HipCausalLM(nn.Module):
                 ops.embed_bwd_sorted_(ids_r, rows_r, view, 1.0 / W, -1)
 
     # ---- inference -----------------------------------------------------------------------------
-    def _hidden_states(self, input_ids, attention_mask=None, position_ids=None, kv_out=None):
+    def _hidden_states(self, input_ids, attention_mask=None, position_ids=None, kv_out=None, attn_out=None):
         """Final-normed hidden states [B*S, H] of a whole (left-padded) batch, nothing saved for backward.  kv_out: optional
         list of per-layer caches [B, cap, 2*Hkv*D]; rows [:S] receive the roped keys and the values (DynamicCache.update,
-        cache_utils.py:408-470)."""
+        cache_utils.py:408-470).  attn_out: optional callable attn_out(layer, qkv, mask, lse, B, S), called after each layer's
+        fused attention (output_attentions, see _AttnSink)."""
+        if attn_out is not None and not self.fused_attention:
+            raise NotImplementedError("attention probabilities are built for the fused attention path only")
         self.sync_optimizer()
         c = self.cfg
         D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.num_key_value_heads
@@ -894,7 +953,9 @@ class HipCausalLM(nn.Module):
             if kv_out is not None:
                 kv_out[i][:, :S - lpad].copy_(qkv.view(B, S, QKV)[:, lpad:, Hq * D:])
             if self.fused_attention:
-                ao, _ = ops.attn_fwd(qkv, mask, B, S, Hq, Hkv, D, scale)
+                ao, lse = ops.attn_fwd(qkv, mask, B, S, Hq, Hkv, D, scale)
+                if attn_out is not None:
+                    attn_out(i, qkv, mask, lse, B, S)
             else:
                 ao, _ = self._attn_materialised(qkv, mask, B, S)
             attn_delta, _ = self._proj(i, "o", ao, self.wo[i].data)
@@ -910,13 +971,13 @@ class HipCausalLM(nn.Module):
             hf = hf.view(B, S, -1)[:, lpad:].reshape(B * S_out, -1)
         return hf
 
-    def _eval_loss(self, input_ids, attention_mask, labels, position_ids):
+    def _eval_loss(self, input_ids, attention_mask, labels, position_ids, attn_out=None):
         """ForCausalLMLoss (loss_utils.py:24-47) without a backward: forward-only hidden states, lm_head + cross entropy
         over the rows whose shifted label is not -100."""
         c = self.cfg
         dev = self.device
         B, S = input_ids.shape
-        hf = self._hidden_states(input_ids, attention_mask, position_ids)
+        hf = self._hidden(input_ids, attention_mask, position_ids, attn_out)
         labels = labels.to(dev)
         shifted = torch.full((B, S), -100, dtype=torch.int64, device=dev)
         shifted[:, :-1] = labels[:, 1:]

@@ -736,6 +736,22 @@ def attn_fwd(qkv, mask, B, S, Hq, Hkv, D, scale):
     return o, lse
 
 
+def attn_probs(qkv, mask, lse, B, S, Hq, Hkv, D, scale, probs=None, psum=None, weight=1.0, accumulate=False):
+    """The attention probabilities behind attn_fwd(qkv, mask, ...) -> (o, lse), recomputed from q, k and lse (ecgb_attn_probs): into `probs` (bf16
+    [B, Hq, S, S], HF's output_attentions layout) and / or `psum` (fp32 [B, S, S]: psum = (psum if accumulate else 0) + weight * sum over the query heads).
+    Rows with no visible key hold 1/S in every column, as the reference's eager softmax gives them.  Returns (probs, psum)."""
+    assert probs is not None or psum is not None, "attn_probs: pass probs and / or psum"
+    if probs is not None:
+        assert probs.dtype == torch.bfloat16 and probs.is_contiguous() and probs.shape == (B, Hq, S, S)
+    if psum is not None:
+        assert psum.dtype == torch.float32 and psum.is_contiguous() and psum.shape == (B, S, S)
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, Hq, S)
+    QKV = qkv.shape[1]
+    _lib.check(_L().ecgb_attn_probs(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _p(mask), _p(lse), _p(probs), _p(psum), float(weight),
+                                    int(bool(accumulate)), B, S, Hq, Hkv, D, float(scale), _st()))
+    return probs, psum
+
+
 def set_stream_grid_cap(n=1 << 20):
     """A/B: the most workgroups glu_fwd / glu_bwd launch (rounds 2-5: 4096)."""
     _lib.check(_L().ecgb_set_stream_grid_cap(int(n)))

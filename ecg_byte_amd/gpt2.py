@@ -63,6 +63,7 @@ class GPT2Config:
 
 class HipGPT2LM(HipCausalLM):
     supports_optimizer_overlap = False   # its forward / backward carry no per-group waits: the optimizer step stays in-stream
+    output_attentions_built = False      # its own _hidden_states: output_attentions raise NotImplementedError
 
     def __init__(self, cfg: GPT2Config, device="cuda", seed: int = 0):
         nn.Module.__init__(self)

@@ -15,7 +15,8 @@ Differences from the reference, all deliberate:
   * `--data_root` / `--runs_root` (defaults: the reference's ./data and ./runs) say where the files live;
   * the decoder is decoder.HipCausalLM (Llama family only), LoRA is decoder.LoraSite, the optimizer decoder.HipAdam
     (Adam + L2 + Noam schedule + clip 1.0 in one kernel), batches come from data_loader.DeviceBatchLoader;
-  * wandb logging (--log) and the attention visualisation (--interpret) are not built."""
+  * wandb logging (--log) is not built; `--interpret` is passed to the LLM wrapper as the reference does (training ignores it) and the
+    interpretation run itself is `python -m ecg_byte_amd.interp_analysis` (runners.interpreter, no plots)."""
 from __future__ import annotations
 
 import argparse

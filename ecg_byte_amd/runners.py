@@ -1,14 +1,18 @@
-"""Mirrors of ecg_byte/runners/train.py (`trainer`, `validater`) and ecg_byte/runners/inference.py (`tester`):
-same arguments, same return dicts, same checkpoint files.  Differences, all on the device side: the gradient
+"""Mirrors of ecg_byte/runners/train.py (`trainer`, `validater`), ecg_byte/runners/inference.py (`tester`) and
+ecg_byte/runners/interpret.py (`interpreter`, without its plots): same arguments, same return dicts, same checkpoint files.  Differences, all on the device side: the gradient
 clip of train.py:26 is folded into `optimizer.step_and_update_lr()` (decoder.HipAdam applies the global-norm
 clip to 1.0 inside the Adam kernel), and in a multi-rank run the gradients are exchanged by
 `parallel.GradAllReduce` during backward instead of DDP hooks.  wandb logging is not mirrored."""
 from __future__ import annotations
 
+import re
+
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from .model_utils import evaluate_strings
+from .tokenizer_utils import decode_text
 
 
 def _save(checkpoint, path, args):
@@ -128,3 +132,93 @@ def tester(model, dataloader, tokenizer, args, extra_metrics=None):
                 counts[key] = counts.get(key, 0) + 1
     return {"metrics": {k: sums[k] / counts[k] for k in sums},
             "qa_results": {"questions": questions, "gt_answers": gt_answers, "gen_answers": gen_answers}}
+
+
+def get_component_indices(batch, tokenizer):
+    """interpret.py:9-36: where the signal (after <sig_start>), the question (after <sig_end>) and the answer (first label that is
+    neither -100 nor the pad id, searched from the question on) begin in the first sequence of the batch."""
+    tokenized_seq = [int(t) for t in batch["tokenized_signal"][0].tolist()]
+    labels = [int(t) for t in batch["quantized_signal_ids_input"][0].tolist()] if "quantized_signal_ids_input" in batch else None
+    sig_start, sig_end = tokenizer.convert_tokens_to_ids("<sig_start>"), tokenizer.convert_tokens_to_ids("<sig_end>")
+    signal_start = 0
+    for i, t in enumerate(tokenized_seq):
+        if t == sig_start:
+            signal_start = i + 1
+            break
+    question_start = signal_start
+    for i in range(signal_start, len(tokenized_seq)):
+        if tokenized_seq[i] == sig_end:
+            question_start = i + 1
+            break
+    answer_start = len(tokenized_seq)
+    if labels is not None:
+        for i in range(question_start, len(labels)):
+            if labels[i] != -100 and labels[i] != tokenizer.pad_token_id:
+                answer_start = i
+                break
+    return signal_start, question_start, answer_start
+
+
+def expand_attention(encoded_ids, attention_sequence, vocab):
+    """interpret.py:106-111: each token's attention repeated once per ECG symbol the token stands for."""
+    expanded_attention = []
+    for token_id, attention_value in zip(encoded_ids, attention_sequence):
+        expanded_attention.extend([attention_value] * len(vocab[token_id]))
+    return expanded_attention
+
+
+def interpreter(model, dataloader, tokenizer, vocab, args):
+    """interpret.py:38-104 without the plots: batch-1 forwards with the attention map averaged over layers and heads (the model's
+    output_attentions="mean" form -- the same [S, S] as the reference's torch.stack(out.attentions).mean(dim=(0, 2))[0]), each component's
+    block of it averaged over its query rows.  The reference reshapes the expanded signal attention to (12, 500) and fails on anything
+    else; here it is (12, n // 12), and a sample whose n is not a multiple of 12 (a truncated signal) is skipped with a printed reason."""
+    model.eval()
+    signal_attentions, signal_seqs, signal_decodes = [], [], []
+    question_attentions, question_seqs = [], []
+    answer_attentions, answer_seqs = [], []
+    previous = getattr(model, "output_attentions", False)
+    model.output_attentions = "mean"
+    try:
+        with torch.no_grad():
+            for step, batch in enumerate(dataloader):
+                if batch is None:
+                    continue
+                signal_start, question_start, answer_start = get_component_indices(batch, tokenizer)
+                out = model(batch)
+                attention = torch.stack(out.attentions).mean(dim=(0, 2))[0]
+                sequence = batch["tokenized_signal"][0]
+                seq_len = len(sequence)
+                signal_seq = sequence[signal_start:question_start]
+                signal_att = attention[signal_start:question_start, signal_start:question_start].mean(dim=0)
+                question_seq = sequence[question_start:answer_start]
+                if len(question_seq) == 0:
+                    continue
+                question_att = attention[question_start:answer_start, question_start:answer_start].mean(dim=0)
+                answer_seq = sequence[answer_start:seq_len - 1]
+                if len(answer_seq) == 0:
+                    continue
+                answer_att = attention[answer_start:seq_len - 1, answer_start:seq_len - 1].mean(dim=0)
+
+                signal_att_np = signal_att.cpu().float().numpy()
+                signal_decoded = tokenizer.decode(signal_seq.cpu().numpy(), skip_special_tokens=True)
+                signal_ids = [int(i) for i in re.findall(r"signal_(\d+)", signal_decoded)]
+                n = len(expand_attention(signal_ids, signal_att_np, vocab))
+                if n % 12:
+                    print(f"Skipping sample {step}: {n} signal symbols are not 12 leads of equal length")
+                    continue
+                signal_seqs.append(signal_seq.cpu().numpy())
+                signal_attentions.append(signal_att_np)
+                question_seqs.append(question_seq.cpu().numpy())
+                question_attentions.append(question_att.cpu().float().numpy())
+                answer_seqs.append(answer_seq.cpu().numpy())
+                answer_attentions.append(answer_att.cpu().float().numpy())
+                signal_decodes.append(decode_text(signal_ids, vocab))
+                if getattr(args, "dev", False) and len(signal_seqs) >= 5:
+                    break
+    finally:
+        model.output_attentions = previous
+    return {
+        "signal": {"sequences": signal_seqs, "attentions": signal_attentions, "signal": signal_decodes},
+        "question": {"sequences": question_seqs, "attentions": question_attentions},
+        "answer": {"sequences": answer_seqs, "attentions": answer_attentions},
+    }

@@ -258,6 +258,18 @@ int ecgb_softmax_bwd(const void *p_dev, void *dp_dev, int batch_heads, int seq, 
 int ecgb_attn_fwd(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
                   const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
                   int n_q_heads, int n_kv_heads, int head_dim, float scale, void *stream);
+/* Attention probabilities of the causal + left-padding mask (HF's output_attentions, modeling_llama.py eager_attention_forward), recomputed from q, k
+ * and the lse that ecgb_attn_fwd wrote (same q / k pointers and strides):
+ *   P[b,h,i,j] = exp2(scale*log2(e) * q[b,i,h].k[b,j,h/(Hq/Hkv)] - lse[b,h,i])   if j <= i and attn_mask[b,j] != 0
+ *              = 0                                                             if key j is not visible to row i
+ *              = 1/S for every j in [0, S)                                     if row i has no visible key (lse = +inf)
+ * p_dev (bf16 [B, Hq, S, S], may be null): P rounded to nearest even.
+ * psum_dev (fp32 [B, S, S], may be null): psum = (accumulate ? psum : 0) + weight * sum over h = 0..Hq-1 of P (fp32, heads added
+ *   in ascending order in registers, one store per element -- the same bits every launch).  At least one of the two is non-null.
+ * head_dim 64, 128 or 256 (else ECGB_ERR_UNSUPPORTED), any seq >= 1; q / k 16-byte aligned with strides multiples of 8 elements. */
+int ecgb_attn_probs(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const float *attn_mask_dev,
+                    const float *lse_dev, void *p_dev, float *psum_dev, float psum_weight, int psum_accumulate,
+                    int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim, float scale, void *stream);
 /* dq/dk/dv from dO (same layout as o).  delta_dev [batch, n_q_heads, seq] fp32 is scratch (rowsum(dO*O)).
  * dK/dV sum over the query heads of each KV group inside the kernel (no atomics). */
 /* head_dim 64 forward and backward: 2 = the lean kernels (default): tiles by LDS-DMA two tiles ahead into a ring of three buffers, the register operand
