@@ -763,7 +763,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_dma_kernel(AttnArgs A)
 //     then the exact path: row maximum, rescale of l and O, new reference.  Tiles that need the causal / padding mask always take the exact path.
 // The bf16 rounding points of P and dS are the ones of the kernels above; what changes is the rounding of the pre-scaled operand (half an ulp
 // of bf16 on q resp. k: the size of the input's own quantisation) and the order of the fp32 sums inside the MFMA.  lse / delta keep their meaning
-// and layout, so every lean kernel can be mixed with the others (tests A/B each one alone).
+// and layout, so every lean kernel can be mixed with the others (tests A/B each one alone) -- up to the pre-scaled operand's rounding: a lean lse
+// and exact scores (or the dK / dV kernel's pre-scaled k) disagree by up to 2^-8 of sum |q k| * scale * log2 e, which matters at large scores.
 // =====================================================================================================
 
 // row operand fragments, pre-scaled: bf16(x * mul) (mul = +-scale * log2 e, or -1 for a sign flip, which is exact)
@@ -2155,8 +2156,10 @@ int check_args(const AttnArgs &A, int D, const char *who)
         ecgb::set_error(std::string(who) + ": row strides must be multiples of 8 elements");
         return ECGB_ERR_UNSUPPORTED;
     }
-    if ((D == 64 ? 6 : 4) * 128 * D + 4 * (((long long)A.S + 63) & ~63ll) > 160 * 1024) {      // tile buffers + the row's key mask in LDS
-        ecgb::set_error(std::string(who) + ": sequence too long for the key mask in LDS (head_dim 256: 8 192 keys, 64: 28 672)");
+    // tile buffers + the row's key mask in LDS; at head_dim 64 also the lean kernels' 64 tile flags (256 bytes), so that every form of the
+    // head dim takes the same lengths (without them 28 609..28 672 keys passed here and failed at the lean kernels' LDS attribute)
+    if ((D == 64 ? 6 : 4) * 128 * D + 4 * (((long long)A.S + 63) & ~63ll) + (D == 64 ? 256 : 0) > 160 * 1024) {
+        ecgb::set_error(std::string(who) + ": sequence too long for the key mask in LDS (head_dim 256: 8 192 keys, 128: 24 576, 64: 28 608)");
         return ECGB_ERR_UNSUPPORTED;
     }
     return ECGB_OK;

@@ -239,6 +239,7 @@ class _AttnSink:
     def __call__(self, i, qkv, mask, lse, B, S):
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
         scale = 1.0 / math.sqrt(D)
+        lse = ops.probs_lse(qkv, mask, lse, B, S, Hq, Hkv, D, scale)     # the lean head_dim-64 forward's lse is not one of exact scores
         if self.mean:
             if self.psum is None:
                 self.psum = torch.empty((B, S, S), dtype=torch.float32, device=qkv.device)

@@ -773,11 +773,30 @@ def set_attn_d256_pass_p(on: bool = False):
     _lib.check(_L().ecgb_set_attn_d256_pass_p(int(bool(on))))
 
 
+_attn_staging = 2
+
+
 def set_attn_fwd_staging(mode: int = 2):
     """head_dim 64 forward / backward kernels: 2 = lean LDS-DMA kernels (default: softmax constants in the MFMA accumulators, deferred running
     maximum), 1 = the round-2 LDS-DMA kernels, 0 = the register-staged kernels (tests, A/B).  With 2: | 0x100 / 0x200 / 0x400 keeps the forward /
     dQ / dK-dV kernel alone on mode 1."""
+    global _attn_staging
     _lib.check(_L().ecgb_set_attn_fwd_staging(int(mode)))
+    _attn_staging = int(mode)
+
+
+def probs_lse(qkv, mask, lse, B, S, Hq, Hkv, D, scale):
+    """The lse to hand to attn_probs for the forward attn_fwd(qkv, mask, ...) ran: `lse` itself, except after the lean head_dim-64 forward.  That
+    kernel forms its scores from q * scale * log2 e rounded to bf16, an error of up to 2^-8 of sum |q k| * scale * log2 e log2 units in its lse
+    (0.1 log2 units at scores of +-40 nats), while attn_probs forms exact fp32 scores; probabilities from the two are off by as much.  Then the
+    round-2 forward (exact bf16 q) runs once more for an lse of the same scores attn_probs forms."""
+    if D != 64 or (_attn_staging & 3) != 2 or (_attn_staging & 0x100):
+        return lse
+    try:
+        set_attn_fwd_staging(_attn_staging | 0x100)
+        return attn_fwd(qkv, mask, B, S, Hq, Hkv, D, scale)[1]
+    finally:
+        set_attn_fwd_staging(_attn_staging & ~0x100)
 
 
 _fuse_rope_bwd = True

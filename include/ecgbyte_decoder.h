@@ -254,7 +254,9 @@ int ecgb_softmax_bwd(const void *p_dev, void *dp_dev, int batch_heads, int seq, 
  * registers, MFMA for QK^T and PV.  q/k/v/o are [batch*seq] rows with the given row strides (elements);
  * query head hq starts at q + hq*head_dim, KV head g at k + g*head_dim (so slices of a fused qkv buffer work).
  * Key j is visible to query i iff j <= i and attn_mask[b, j] != 0; rows without a visible key give zeros.
- * lse_dev [batch, n_q_heads, seq] fp32 is saved for the backward.  head_dim 64 (Llama, GPT-2), 128 or 256 (Gemma). */
+ * lse_dev [batch, n_q_heads, seq] fp32 is saved for the backward.  head_dim 64 (Llama, GPT-2), 128 or 256 (Gemma).
+ * The row's key mask lives in LDS: seq at most 28 608 (head_dim 64), 24 576 (128) or 8 192 (256); longer is ECGB_ERR_UNSUPPORTED
+ * before any launch (ecgb_attn_bwd likewise). */
 int ecgb_attn_fwd(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
                   const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
                   int n_q_heads, int n_kv_heads, int head_dim, float scale, void *stream);
@@ -266,7 +268,10 @@ int ecgb_attn_fwd(const void *q_dev, long long ldq, const void *k_dev, long long
  * p_dev (bf16 [B, Hq, S, S], may be null): P rounded to nearest even.
  * psum_dev (fp32 [B, S, S], may be null): psum = (accumulate ? psum : 0) + weight * sum over h = 0..Hq-1 of P (fp32, heads added
  *   in ascending order in registers, one store per element -- the same bits every launch).  At least one of the two is non-null.
- * head_dim 64, 128 or 256 (else ECGB_ERR_UNSUPPORTED), any seq >= 1; q / k 16-byte aligned with strides multiples of 8 elements. */
+ * head_dim 64, 128 or 256 (else ECGB_ERR_UNSUPPORTED), any seq >= 1; q / k 16-byte aligned with strides multiples of 8 elements.
+ * The lse must be one of these exact fp32 scores: at head_dim 64 that of the round-2 forward (ecgb_set_attn_fwd_staging 1, or 2 | 0x100), NOT of the
+ * default lean forward, whose scores come from q * scale * log2 e rounded to bf16 -- an lse off by up to 2^-8 * sum |q k| * scale * log2 e log2
+ * units, which the probabilities inherit (0.1 absolute at scores of +-40 nats).  decoder_ops.probs_lse gives the right one. */
 int ecgb_attn_probs(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const float *attn_mask_dev,
                     const float *lse_dev, void *p_dev, float *psum_dev, float psum_weight, int psum_accumulate,
                     int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim, float scale, void *stream);
@@ -275,7 +280,11 @@ int ecgb_attn_probs(const void *q_dev, long long ldq, const void *k_dev, long lo
 /* head_dim 64 forward and backward: 2 = the lean kernels (default): tiles by LDS-DMA two tiles ahead into a ring of three buffers, the register operand
  * pre-scaled by scale * log2 e, the softmax row constants (running maximum / log-sum-exp / delta) as the initial accumulators of the score products,
  * forward running maximum deferred; 1 = the round-2 LDS-DMA kernels; 0 = the register-staged kernels (1 and 0 are bit-identical to each other and kept
- * for A/B and as cross-checks).  With 2, | 0x100 / 0x200 / 0x400 keeps the forward / dQ / dK-dV kernel alone on mode 1.  ECGB_ERR_INVALID otherwise. */
+ * for A/B and as cross-checks).  With 2, | 0x100 / 0x200 / 0x400 keeps the forward / dQ / dK-dV kernel alone on mode 1.  ECGB_ERR_INVALID otherwise.
+ * Precision of the lean kernels: the pre-scaled operand (q in the forward and dQ, k in dK / dV) is rounded to bf16, so their scores are off by up to
+ * 2^-8 * sum |q k| * scale * log2 e log2 units -- negligible at a few nats, 0.1 at +-40 nats, whole units at scores of hundreds.  The forward and dQ
+ * round the same q, so they agree with each other; dK / dV (k rounded) and any kernel mixed in on mode 1 (exact scores) do not agree with a lean
+ * lse to better than that. */
 int ecgb_set_attn_fwd_staging(int mode);
 /* waves per workgroup of the lean kernels: 4 (default) or 8 (a K / V tile serves gcd(G, 8) query heads x 256 / gcd rows; A/B). */
 int ecgb_set_attn_lean_waves(int waves);
