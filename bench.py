@@ -11,12 +11,17 @@ the data path: records are independent).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run measures the headline figure only: it generates the records, warms up, times the steps,
+writes `--dump-outputs` and prints the line.  `--full` also runs every other leg and check of the line
+(CPU baselines, batch sweep, C1, the C3 train legs, C5, the device self-check, the tokenizer trainer,
+the offline conditioning); the --no-* options trim such a run.
+
 `--dump-outputs DIR` also writes what the last timed step returned (counts, a seeded sample of records' token ids) as
 DIR/*.npy, for comparing two builds output for output (dump_encode_outputs).
 
 Rank 0 prints ONE JSON line.  `value` = token ids produced per second by the whole job
 (inputs already resident in HBM).  `roofline` prices the timed kernels against HBM with the
-algorithmic bytes of SURVEY.md §8d: 8*12*L read + 4*T written per record.  `cpu_baseline` times
+algorithmic bytes of SURVEY.md §8d: 8*12*L read + 4*T written per record.  `cpu_baseline` (--full) times
 the CPU oracle (a C port of the reference's Rust encoder + numpy quantiser) on this box's host
 cores over a bounded sample of the same records.
 """
@@ -887,6 +892,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--batch", type=int, default=4096, help="records per GPU")
     ap.add_argument("--L", type=int, default=5000, help="samples per lead")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, run every other leg and check of the line (CPU baselines, batch sweep, C1, train legs, C5, device "
+                         "self-check, tokenizer trainer, offline conditioning); the options below shape that run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the train-step part (encode metric only)")
     ap.add_argument("--train-batch", type=int, default=32, help="samples per GPU per train step")
@@ -903,6 +911,12 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run: the headline figure only (every leg below is skipped); an option that changes a train leg would be silently void
+        for opt in ("lora", "full_logits", "overlap_optimizer"):
+            if getattr(args, opt):
+                ap.error(f"--{opt.replace('_', '-')} shapes a train leg, which only a --full run has")
+        args.no_cpu_baseline = args.no_train = args.no_c1 = args.no_c5 = args.no_extras = True
     # --gpus N must be what the launcher started: checked before anything is generated or initialised (exit 2, no line); the process group's own size is checked again below
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
         sys.stderr.write(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={os.environ.get('WORLD_SIZE', '1')}: start it as python -m torch.distributed.run --nproc-per-node {args.gpus} bench.py --gpus {args.gpus}\n")
@@ -927,7 +941,7 @@ def main():
     workers = int(os.environ.get("ECGB_BENCH_WORKERS", max(1, min(8, (os.cpu_count() or 1) // max(1, world)))))   # 1: no fork pool (profiler runs)
     x = make_signals(args.batch, args.L, seed=0, start=rank * args.batch, workers=workers)   # rank r owns records rB..rB+B-1
     loader_dir = None
-    serial = gpu_serial() if rank == 0 else None               # (before HIP is up in this process)
+    serial = gpu_serial() if rank == 0 and args.full else None   # (before HIP is up in this process)
     x_train = None if args.no_train else make_signals(args.train_batch, args.L, seed=0,
                                                       start=10_000_000 + rank * args.train_batch, workers=workers)
     # the tokenizer trainer's corpus (2 000 records, seed 1: what tests/golden/tokenizer_c2.pkl was trained on) -- generated here, before HIP is up, like the rest
@@ -1056,7 +1070,7 @@ def main():
     if rank == 0 and world == 1 and not args.no_c5 and not args.no_train:
         c5 = bench_c5(args, dev)
     extras = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         extras["device"] = device_selfcheck(serial)
     if rank == 0 and world == 1 and not args.no_extras and L == 5000:
         extras["trainer"] = bench_trainer(pc, L, x_corpus)

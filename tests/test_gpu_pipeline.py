@@ -203,7 +203,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "512", "--steps", "3",
-           "--warmup", "1", "--train-batch", "2", "--train-steps", "2", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--train-batch", "2", "--train-steps", "2", "--no-cpu-baseline"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -219,7 +219,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
 
 
 def test_bench_line_contract_single_gpu():
-    """The one JSON line bench.py prints (N = 1, encode leg with its CPU baseline; the train leg is skipped here, the
+    """The one JSON line bench.py --full prints (N = 1, encode leg with its CPU baseline; the train leg is skipped here, the
     two-rank test above runs it): every key the driver and SURVEY 8d ask for, with consistent values."""
     import subprocess
     import sys
@@ -227,7 +227,7 @@ def test_bench_line_contract_single_gpu():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--no-train"],
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-train"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -250,6 +250,29 @@ def test_bench_line_contract_single_gpu():
     c = out["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["unit"] == "tokens/s" and c["value"] > 0 and "records" in c["sample"]
     assert c["quantiser_python_style_symbols_per_s"] < c["quantiser_c_symbols_per_s"]
+
+
+def test_bench_plain_run_is_the_headline_only():
+    """bench.py without --full sets up, warms up, times the steps and prints the line: the headline keys as a --full run has them, and
+    none of the --full legs or checks in it."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--batch", "512"],
+                         cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["metric"] == "ecg_tokens_per_sec_encode" and out["unit"] == "tokens/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f64->u8->u32" and out["steps"] == 5 and out["warmup"] == 2 and out["config"]["records_per_gpu"] == 512
+    n_tok = out["tokens_per_record"] * 512
+    assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] * 1e-3 - n_tok) < 1e-4 * n_tok
+    for k in ("cpu_baseline", "batch_sweep", "c1", "c5", "train", "device", "trainer", "preprocess"):
+        assert k not in out, k
 
 
 def test_bench_dump_outputs_are_the_oracle_ids():

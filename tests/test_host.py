@@ -368,6 +368,19 @@ def test_bench_refuses_a_world_size_other_than_gpus():
     assert r.returncode == 2 and r.stdout.strip() == ""
 
 
+def test_bench_refuses_train_leg_options_without_full():
+    """--lora, --full-logits and --overlap-optimizer shape a train leg, which only bench.py --full runs: without --full they exit 2 before anything
+    is generated or initialised, instead of printing a headline line they did not apply to."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    for opt in ("--lora", "--full-logits", "--overlap-optimizer"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", opt],
+                           env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and r.stdout.strip() == "" and "--full" in r.stderr, opt
+
+
 def test_four_wave_gemm_refuses_operands_its_32_bit_dma_offsets_cannot_span(lib):
     """The four-wave GEMM sets its DMA descriptor once per output tile and walks the contraction with 32-bit scalar offsets: an operand stored as contraction rows
     reaches (K + 15) * ld * 2 bytes, a row operand 63 * ld * 2 + K * 2.  Operands of 4 GiB and more must go to the eight-wave kernels (round 4's advisor finding:
