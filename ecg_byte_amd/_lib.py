@@ -115,6 +115,24 @@ def lib():
     L.ecgb_wavelet_denoise_f64.restype = C.c_int
     L.ecgb_nonfinite_records_f64.argtypes = [vp, C.c_int, sz, vp, vp]
     L.ecgb_nonfinite_records_f64.restype = C.c_int
+    ip, dp = C.c_void_p, C.c_void_p
+    L.ecgb_morph_features_lds_bytes.argtypes = [C.c_int]
+    L.ecgb_morph_features_lds_bytes.restype = sz
+    L.ecgb_morph_features_f64.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    L.ecgb_morph_features_f64.restype = C.c_int
+    L.ecgb_kmpp_init_f64.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, dp, vp]
+    L.ecgb_kmpp_init_f64.restype = C.c_int
+    L.ecgb_kmpp_step_f64.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, ip, ip, ip, C.c_int, dp, dp, dp, dp, vp]
+    L.ecgb_kmpp_step_f64.restype = C.c_int
+    L.ecgb_kmeans_lloyd_f64.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, C.c_double, C.c_int, C.c_int,
+                                        dp, dp, dp, dp, ip, ip, ip, ip, vp]
+    L.ecgb_kmeans_lloyd_f64.restype = C.c_int
+    L.ecgb_kmeans_finish_f64.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, ip, ip, ip, dp, vp]
+    L.ecgb_kmeans_finish_f64.restype = C.c_int
+    L.ecgb_silhouette_f64.argtypes = [vp, dp, C.c_int, C.c_int, ip, ip, C.c_int, ip, dp, vp]
+    L.ecgb_silhouette_f64.restype = C.c_int
+    L.ecgb_dbscan_f64.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_int, ip, ip, vp]
+    L.ecgb_dbscan_f64.restype = C.c_int
     i32 = C.c_int32
     L.ecgb_assemble_hip.argtypes = [vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, i32, i32, i32, i32, i32, u32,
                                     C.c_int, u32, vp, vp, vp, vp, vp, vp]

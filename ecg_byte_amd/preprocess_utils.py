@@ -350,3 +350,40 @@ def process_and_save_batch(segments, texts, first_index, split_name, data, seg_l
                 json.dump(texts[int(orig)], f)
         written.append(i)
     return written
+
+
+# ---- the sampling step (preprocess_utils.py:259-462): reference names on top of ecg_byte_amd/morphology.py -----------------------------------------------------
+def extract_features(ecg, sampling_rate=250):
+    """preprocess_utils.py:259-347: 24 values per lead.  `ecg`: one (12, L) numpy record -> numpy [288], or a float64 CUDA batch [records, 12, L]
+    -> [records, 288] on the device.  Only the rate the reference's driver uses (250) is built."""
+    from . import morphology
+    if sampling_rate != 250:
+        raise NotImplementedError("analyze_morphologies calls extract_features at sampling_rate 250: only that is built")
+    if torch.is_tensor(ecg):
+        return morphology.features(ecg)[0]
+    x = torch.from_numpy(np.ascontiguousarray(ecg, dtype=np.float64)[None]).cuda()
+    return morphology.features(x)[0][0].cpu().numpy()
+
+
+def analyze_morphologies(directory, max_clusters=100, subset_size=10000, **kw):
+    """preprocess_utils.py:349-393: (file_paths, clusters, n_clusters); see morphology.analyze_morphologies."""
+    from . import morphology
+    return morphology.analyze_morphologies(directory, max_clusters, subset_size, **kw)
+
+
+def find_optimal_clusters(data, max_clusters, **kw):
+    """preprocess_utils.py:395-439 (no PNG; see morphology.find_optimal_clusters)."""
+    from . import morphology
+    return morphology.find_optimal_clusters(data, max_clusters, **kw)
+
+
+def find_elbow_point(inertias):
+    """preprocess_utils.py:441-445."""
+    from . import morphology
+    return morphology.find_elbow_point(inertias)
+
+
+def stratified_sampling(file_paths, clusters, n_samples=100000, seed=0):
+    """preprocess_utils.py:447-462, seeded (see morphology.stratified_sampling)."""
+    from . import morphology
+    return morphology.stratified_sampling(file_paths, clusters, n_samples, seed=seed)

@@ -255,6 +255,40 @@ int ecgb_resample_cubic_planar_f64(const double *x_dev, double *y_dev, int recor
  * flags_dev[r] = 1 if record r (per_record consecutive doubles) holds a NaN or an infinity; flags_dev must be zero on entry.  One pass at memory speed. */
 int ecgb_nonfinite_records_f64(const double *x_dev, int records, size_t per_record, unsigned char *flags_dev, void *stream);
 
+/* ---- record sampling (ecg_byte/utils/preprocess_utils.py:259-462, preprocess/sample_ecg.py), morphology.hip; all float64 ----
+ * ecgb_morph_features_f64: extract_features (:259-347) for x_dev [records][12][L], out_dev [records][288] (24 values per lead, lead by lead, the
+ *   reference's order), sampling rate 250.  flags_dev [records], zeroed by the caller: 1 where a record holds a NaN / infinity (its features are
+ *   then meaningless).  8 <= L <= 5000, else ECGB_ERR_UNSUPPORTED.  Order statistics, the dominant frequency, peak positions and the values
+ *   derived from them follow numpy / scipy operation by operation; the other sums agree to rounding.  find_peaks' distance pass orders equal
+ *   heights as numpy's argsort does for up to 16 peaks (stable: the later of two tied peaks wins); beyond 16 numpy's order is unspecified and
+ *   parity on exactly equal heights is not claimed there.
+ * k-means (KMeans(k, random_state=42, n_init=10), Lloyd, sklearn 1.5.2), a batch of `runs` runs over one centered X [n][D], 1 <= D <= 288: run r
+ *   has k_dev[r] centers at rows off_dev[r] .. of the [rows][D] center arrays and its labels at labels_dev + r * n.
+ *   ecgb_kmpp_init_f64    xsq = row norms; center 0 = X[first_dev[r]]; closest [runs][n]; pot [runs]
+ *   ecgb_kmpp_step_f64    center c of the runs with k > c: u_dev [runs][8] are numpy's uniform draws (the first trials_dev[r] used)
+ *   ecgb_kmeans_lloyd_f64 `iters` Lloyd iterations of the runs whose state_dev is 0 (running); a run ends in state 1 (labels unchanged) or 2
+ *                         (shift <= tol or max_iter: one more E-step due); labels start at -1, state, changed, n_iter at 0.  k <= 1024.
+ *   ecgb_kmeans_finish_f64 the E-step of the state-2 runs, then inertia_dev [runs]; every state becomes 1.
+ *   Parity with sklearn does not cover two clusters emptying in one iteration (numpy's argpartition order is unspecified there).
+ * ecgb_silhouette_f64: silhouette_samples for the m subset rows idx_dev, grouped by label (label l at positions loff_dev[l] .. loff_dev[l+1]-1,
+ *   lab_of_pos_dev[p] its label); sklearn's expanded euclidean distances, s = 0 for singletons; s_dev [m] in idx order.
+ * ecgb_dbscan_f64: DBSCAN(eps, min_samples) labels (sklearn's numbering: components of core points in order of their smallest core index, a
+ *   border point takes the smallest label among its core neighbours, noise -1); work_dev: 3 n + 1 ints.  Synchronises the stream. */
+size_t ecgb_morph_features_lds_bytes(int L);
+int ecgb_morph_features_f64(const double *x_dev, int records, int L, double *out_dev, unsigned char *flags_dev, void *stream);
+int ecgb_kmpp_init_f64(const double *X, int n, int D, int runs, const int *off_dev, const int *first_dev, double *xsq_dev, double *centers_dev,
+                       double *closest_dev, double *pot_dev, void *stream);
+int ecgb_kmpp_step_f64(const double *X, const double *xsq_dev, int n, int D, int runs, const int *k_dev, const int *off_dev, const int *trials_dev,
+                       int c, const double *u_dev, double *centers_dev, double *closest_dev, double *pot_dev, void *stream);
+int ecgb_kmeans_lloyd_f64(const double *X, int n, int D, int runs, int k_max, int rows, const int *k_dev, const int *off_dev, double tol,
+                          int max_iter, int iters, double *centers_dev, double *sums_dev, double *weights_dev, double *cn_dev,
+                          int *labels_dev, int *state_dev, int *changed_dev, int *n_iter_dev, void *stream);
+int ecgb_kmeans_finish_f64(const double *X, int n, int D, int runs, int rows, const int *k_dev, const int *off_dev, const double *centers_dev,
+                           double *cn_dev, int *labels_dev, int *state_dev, int *changed_dev, double *inertia_dev, void *stream);
+int ecgb_silhouette_f64(const double *X, const double *xsq_dev, int D, int m, const int *idx_dev, const int *loff_dev, int n_labels,
+                        const int *lab_of_pos_dev, double *s_dev, void *stream);
+int ecgb_dbscan_f64(const double *X, int n, int D, double eps, int min_samples, int *labels_dev, int *work_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
