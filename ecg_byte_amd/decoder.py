@@ -20,6 +20,7 @@ whose (shifted) label is not -100 -- identical loss and gradients, a fraction of
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from dataclasses import dataclass, field
 from types import SimpleNamespace
@@ -264,6 +265,11 @@ class HipCausalLM(nn.Module):
     decode_attn_one = True      # a decode step's RoPE + append + attention as one launch where the shape allows (ops.decode_one_ok); False: round 4's four launches, the same bits
     decode_lora_one = False     # True: a decode step's o / down adapter sites form t = scale * x A^T inside the projection's launch (ops.gemm_nt_lora_decode: two launches a layer less, the same
                                 # bits) -- measured 503 against 508 tokens/s at the C5 shape: two dependent dot products and a hand-over between XCDs take what the launch boundary took
+    decode_fused = False        # (opt-in: the fused kernels of csrc/decode.hip are bit-exact but measured no faster than the separate ones at the C5 shape -- 2.20 against 2.14 ms a token; every
+                                #  kernel of the step sits on the ~5 us a dependent launch of a replayed graph costs, whatever it fuses: profiles/r05/README.md)
+    decode_fused_attn = False   # the fused step's attention: round 4's kernels (RoPE + append, scores, values, combine) unless this is set -- the two-launch form of csrc/decode.hip is bit-exact
+                                # and reads a KV group's keys once, but measured SLOWER at the C5 shape (82 against 25 us a layer: profiles/r05/README.md); kept for the record and the tests
+
     def __init__(self, cfg: DecoderConfig, device="cuda", seed: int = 0):
         super().__init__()
         self.cfg = cfg
@@ -393,7 +399,7 @@ class HipCausalLM(nn.Module):
             with torch.no_grad():
                 B, S = input_ids.shape
                 sink = self._attn_sink(output_attentions)
-                hf = self._hidden(input_ids, attention_mask, position_ids, sink)
+                hf = self._hidden_states(input_ids, attention_mask, position_ids, attn_out=sink)
                 logits = ops.gemm_nt(hf, self.embed.data)[:, :self.cfg.vocab_size].float().view(B, S, -1)
             return SimpleNamespace(loss=None, logits=logits, attentions=sink.result() if sink else None)
         if not torch.is_grad_enabled():   # validation: loss only, nothing kept for a backward
@@ -415,11 +421,6 @@ class HipCausalLM(nn.Module):
                                       f"this model (head_dim {self.cfg.head_dim}, {type(self).__name__}) does not provide them")
         c = self.cfg
         return _AttnSink(c.num_hidden_layers, c.num_attention_heads, c.num_key_value_heads, c.head_dim, output_attentions == "mean")
-
-    def _hidden(self, input_ids, attention_mask, position_ids, sink):
-        if sink is None:
-            return self._hidden_states(input_ids, attention_mask, position_ids)
-        return self._hidden_states(input_ids, attention_mask, position_ids, attn_out=sink)
 
     def resize_token_embeddings(self, n: int):
         """transformers/modeling_utils.py:2080-2176, with new rows drawn as modeling_utils.py:2464-2489 does:
@@ -609,10 +610,46 @@ class HipCausalLM(nn.Module):
             hm = ops.glu_fwd(gu, gelu_tanh=self.gemma)
         return gu, hm, None
 
+    def _norm(self, i, key, x, delta, with_t=False):
+        """The RMSNorm in front of layer i's "qkv" or "gu" projection over x (+ delta): returns (h, x + delta, t).  t = scale * h A^T of that site's adapters, formed by
+        the norm kernel on its way out (one launch less, the same bits), when the caller asks for it (with_t), adapters are on and the model is in eval mode; else None
+        (training mode, also under torch.no_grad(): the site forms its own t, with its dropout)."""
+        w = (self.ln1 if key == "qkv" else self.ln2)[i].data
+        if with_t and self.lora is not None and not self.training:
+            site = self.lora[i][key]
+            h, _, x, t = ops.rmsnorm_fwd(x, w, self.cfg.rms_norm_eps, residual=delta, gemma=self.gemma, lora=(site.A.data, site.scale))
+            return h, x, t
+        h, _, x = ops.rmsnorm_fwd(x, w, self.cfg.rms_norm_eps, residual=delta, gemma=self.gemma)
+        return h, x, None
+
     def _rope_tables(self, position_ids):
         pos = position_ids.reshape(-1).float()
         fr = pos[:, None] * self.inv_freq[None, :].float()
         return fr.cos().contiguous(), fr.sin().contiguous()
+
+    def _prep(self, input_ids, attention_mask, position_ids, labels=None, pad=False):
+        """A batch on the model's device: (input_ids, mask fp32, position_ids, labels or None, B, S, lpad), the mask and the positions defaulted (all visible, 0..S-1).
+        pad: S is brought to a multiple of 64 by lpad columns on the LEFT (S includes them)."""
+        dev = self.device
+        ops.require_current(dev)
+        input_ids = input_ids.to(dev).contiguous()
+        B, S = input_ids.shape
+        mask = (attention_mask.to(dev).float() if attention_mask is not None else torch.ones(B, S, device=dev)).contiguous()
+        if position_ids is None:
+            position_ids = torch.arange(S, device=dev)[None].expand(B, S)
+        position_ids = position_ids.to(dev)
+        if labels is not None:
+            labels = labels.to(dev)
+        lpad = 0
+        if pad and S % 64:   # the GEMM K-step is 64 rows/columns: masked, unlabelled positions on the LEFT change neither the loss nor any
+            lpad = 64 - S % 64   # gradient (the reference's default --pad_to_max 1000 gives rows of 1004, data_loader.py:123)
+            input_ids = torch.cat([torch.zeros((B, lpad), dtype=input_ids.dtype, device=dev), input_ids], 1).contiguous()
+            mask = torch.cat([torch.zeros((B, lpad), device=dev), mask], 1).contiguous()
+            position_ids = torch.cat([torch.zeros((B, lpad), dtype=position_ids.dtype, device=dev), position_ids], 1)
+            if labels is not None:
+                labels = torch.cat([torch.full((B, lpad), -100, dtype=labels.dtype, device=dev), labels], 1)
+            S += lpad
+        return input_ids, mask, position_ids, labels, B, S, lpad
 
     def _attn_materialised(self, qkv, mask, B, S, drop=None):
         """Attention through the [B*Hq, S, S] score tensor (head-batched GEMMs + softmax kernel): any head_dim that is a
@@ -770,28 +807,10 @@ class HipCausalLM(nn.Module):
     # ---- forward ------------------------------------------------------------------------------
     def _forward_loss(self, input_ids, attention_mask, labels, position_ids):
         c = self.cfg
-        H, I, D, Hq, Hkv = c.hidden_size, c.intermediate_size, c.head_dim, c.num_attention_heads, c.num_key_value_heads
-        G = Hq // Hkv
-        dev = self.device
-        ops.require_current(dev)
-        input_ids = input_ids.to(dev).contiguous()
-        B, S = input_ids.shape
-        mask = (attention_mask.to(dev).float() if attention_mask is not None else torch.ones(B, S, device=dev)).contiguous()
-        if position_ids is None:
-            position_ids = torch.arange(S, device=dev)[None].expand(B, S)
-        position_ids = position_ids.to(dev)
-        labels = labels.to(dev)
-        if S % 64:   # the GEMM K-step is 64 rows/columns: masked, unlabelled positions on the LEFT change neither the loss nor any
-            lpad = 64 - S % 64   # gradient (the reference's default --pad_to_max 1000 gives rows of 1004, data_loader.py:123)
-            input_ids = torch.cat([torch.zeros((B, lpad), dtype=input_ids.dtype, device=dev), input_ids], 1).contiguous()
-            mask = torch.cat([torch.zeros((B, lpad), device=dev), mask], 1).contiguous()
-            position_ids = torch.cat([torch.zeros((B, lpad), dtype=position_ids.dtype, device=dev), position_ids], 1)
-            labels = torch.cat([torch.full((B, lpad), -100, dtype=labels.dtype, device=dev), labels], 1)
-            S += lpad
-        T = B * S
+        D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.num_key_value_heads
+        input_ids, mask, position_ids, labels, B, S, _ = self._prep(input_ids, attention_mask, position_ids, labels, pad=True)
         cos, sin = self._rope_tables(position_ids)
         rope = (cos, sin, (Hq + Hkv) * D)                                 # what the q|k|v projection rotates on its way out
-        QKV = self.qkv
         scale = 1.0 / math.sqrt(D)
         saved = []
         self._wait_group("embed")                                    # (an overlapped optimizer step: this group's update has landed)
@@ -819,6 +838,17 @@ class HipCausalLM(nn.Module):
         self._saved = (saved, input_ids, mask, cos, sin, (xf, rstdf), dhf, (B, S))
         return loss.squeeze(0)
 
+    def _loss_rows(self, labels, B, S, all_rows=False):
+        """ForCausalLMLoss's shift (loss_utils.py:39-41: row t predicts labels[t+1]) and the rows the head runs over: (shifted labels [B*S], 1 / their count,
+        indices of the rows whose shifted label is not -100 -- or of every row: all_rows)."""
+        dev = self.device
+        shifted = torch.full((B, S), -100, dtype=torch.int64, device=dev)
+        shifted[:, :-1] = labels[:, 1:]
+        shifted = shifted.view(-1)
+        inv_count = ops.count_labels(shifted, self.cfg.vocab_size)
+        rows = torch.arange(B * S, device=dev) if all_rows else torch.nonzero(shifted != -100).view(-1)
+        return shifted, inv_count, rows
+
     def _loss_head(self, hf, labels, B, S):
         """Tied lm_head + ForCausalLMLoss (loss_utils.py:24-47) over the final hidden states hf [B*S, H]: returns (loss, d loss / d hf)
         and leaves d loss / d E of the head in self.embed_grad_head (bf16 [v_pad, H]: the table's slice of the flat gradient buffer, or a buffer of
@@ -827,13 +857,8 @@ class HipCausalLM(nn.Module):
         H = c.hidden_size
         dev = self.device
         T = B * S
-        # ---- loss head: ForCausalLMLoss shifts (loss_utils.py:39-41): row t predicts labels[t+1]
-        shifted = torch.full((B, S), -100, dtype=torch.int64, device=dev)
-        shifted[:, :-1] = labels[:, 1:]
-        shifted = shifted.view(-1)
+        shifted, inv_count, rows = self._loss_rows(labels, B, S, all_rows=self.full_logits)
         self._unlabelled_rows = shifted == -100                          # (backward: a row takes no gradient only if it is masked AND carries no loss)
-        inv_count = ops.count_labels(shifted, c.vocab_size)
-        rows = torch.arange(T, device=dev) if self.full_logits else torch.nonzero(shifted != -100).view(-1)
         loss = torch.zeros(1, dtype=torch.float32, device=dev)
         frozen = self.lora is not None
         if not frozen:
@@ -927,65 +952,51 @@ class HipCausalLM(nn.Module):
         self.sync_optimizer()
         c = self.cfg
         D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.num_key_value_heads
-        dev = self.device
-        ops.require_current(dev)
-        input_ids = input_ids.to(dev).contiguous()
-        B, S = input_ids.shape
-        mask = (attention_mask.to(dev).float() if attention_mask is not None else torch.ones(B, S, device=dev)).contiguous()
-        if position_ids is None:
-            position_ids = torch.arange(S, device=dev)[None].expand(B, S)
-        position_ids = position_ids.to(dev)
-        lpad = 0
-        if not self.fused_attention and S % 64:   # the materialised path needs S % 64 == 0: masked positions on the LEFT change nothing
-            lpad = 64 - S % 64
-            input_ids = torch.cat([torch.zeros((B, lpad), dtype=input_ids.dtype, device=dev), input_ids], 1).contiguous()
-            mask = torch.cat([torch.zeros((B, lpad), device=dev), mask], 1).contiguous()
-            position_ids = torch.cat([torch.zeros((B, lpad), dtype=position_ids.dtype, device=dev), position_ids], 1)
-            S_out, S = S, S + lpad
+        # (the materialised path needs S % 64 == 0: masked positions on the LEFT change nothing)
+        input_ids, mask, position_ids, _, B, S, lpad = self._prep(input_ids, attention_mask, position_ids, pad=not self.fused_attention)
         cos, sin = self._rope_tables(position_ids)
         rope = (cos, sin, (Hq + Hkv) * D)                                 # what the q|k|v projection rotates on its way out
-        QKV = self.qkv
         scale = 1.0 / math.sqrt(D)
-        x = ops.embed_fwd(input_ids.view(-1), self.embed.data, self.embed_scale)
-        delta = None
-        for i in range(c.num_hidden_layers):
-            h1, _, x = ops.rmsnorm_fwd(x, self.ln1[i].data, c.rms_norm_eps, residual=delta, gemma=self.gemma)
-            qkv, _ = self._proj(i, "qkv", h1, self.wqkv[i].data, rope=rope)
+
+        def attend(i, qkv):
             if kv_out is not None:
-                kv_out[i][:, :S - lpad].copy_(qkv.view(B, S, QKV)[:, lpad:, Hq * D:])
-            if self.fused_attention:
-                ao, lse = ops.attn_fwd(qkv, mask, B, S, Hq, Hkv, D, scale)
-                if attn_out is not None:
-                    attn_out(i, qkv, mask, lse, B, S)
-            else:
-                ao, _ = self._attn_materialised(qkv, mask, B, S)
-            attn_delta, _ = self._proj(i, "o", ao, self.wo[i].data)
-            if self.lora is not None and not self.training:
-                site = self.lora[i]["gu"]
-                h2, _, x, t2 = ops.rmsnorm_fwd(x, self.ln2[i].data, c.rms_norm_eps, residual=attn_delta, gemma=self.gemma, lora=(site.A.data, site.scale))
-            else:
-                (h2, _, x), t2 = ops.rmsnorm_fwd(x, self.ln2[i].data, c.rms_norm_eps, residual=attn_delta, gemma=self.gemma), None
-            _, hm, _ = self._proj_glu(i, h2, keep_gu=False, t_pre=t2)
-            delta, _ = self._proj(i, "down", hm, self.wdown[i].data)
+                kv_out[i][:, :S - lpad].copy_(qkv.view(B, S, self.qkv)[:, lpad:, Hq * D:])
+            if not self.fused_attention:
+                return self._attn_materialised(qkv, mask, B, S)[0]
+            ao, lse = ops.attn_fwd(qkv, mask, B, S, Hq, Hkv, D, scale)
+            if attn_out is not None:
+                attn_out(i, qkv, mask, lse, B, S)
+            return ao
+
+        x, delta = ops.embed_fwd(input_ids.view(-1), self.embed.data, self.embed_scale), None
+        for i in range(c.num_hidden_layers):
+            # norm_t: here only the gate|up site takes its t from the norm (the q|k|v site forms its own inside LoraSite.project, ecgb_lora_down) while a decode step
+            # passes both -- how the code stands today, not a measured choice: naming "qkv" here too would change this path's launches
+            x, delta = self._layer_infer(i, x, delta, attend, rope=rope, norm_t=("gu",))
         hf, _, _ = ops.rmsnorm_fwd(x, self.norm.data, c.rms_norm_eps, residual=delta, gemma=self.gemma)
         if lpad:
-            hf = hf.view(B, S, -1)[:, lpad:].reshape(B * S_out, -1)
+            hf = hf.view(B, S, -1)[:, lpad:].reshape(B * (S - lpad), -1)
         return hf
+
+    def _layer_infer(self, i, x, delta, attend, rope=None, norm_t=(), sync=None):
+        """Layer i without anything kept for a backward: (x, delta) -> (x + delta + the attention's share, the MLP's share).  attend(i, qkv) is the caller's attention:
+        a whole batch (_hidden_states, with rope: the q|k|v projection rotates q and k) or one new token against the caches (_decode_step: RoPE inside the attention).
+        norm_t: the adapter sites among "qkv", "gu" whose t the norm in front of them forms (see _norm); sync: LoraSite.project's, for the o and down sites."""
+        h1, x, t1 = self._norm(i, "qkv", x, delta, "qkv" in norm_t)
+        qkv, _ = self._proj(i, "qkv", h1, self.wqkv[i].data, rope=rope, t_pre=t1)
+        attn_delta, _ = self._proj(i, "o", attend(i, qkv), self.wo[i].data, sync=sync)
+        h2, x, t2 = self._norm(i, "gu", x, attn_delta, "gu" in norm_t)
+        _, hm, _ = self._proj_glu(i, h2, keep_gu=False, t_pre=t2)
+        return x, self._proj(i, "down", hm, self.wdown[i].data, sync=sync)[0]
 
     def _eval_loss(self, input_ids, attention_mask, labels, position_ids, attn_out=None):
         """ForCausalLMLoss (loss_utils.py:24-47) without a backward: forward-only hidden states, lm_head + cross entropy
         over the rows whose shifted label is not -100."""
         c = self.cfg
-        dev = self.device
         B, S = input_ids.shape
-        hf = self._hidden(input_ids, attention_mask, position_ids, attn_out)
-        labels = labels.to(dev)
-        shifted = torch.full((B, S), -100, dtype=torch.int64, device=dev)
-        shifted[:, :-1] = labels[:, 1:]
-        shifted = shifted.view(-1)
-        inv_count = ops.count_labels(shifted, c.vocab_size)
-        rows = torch.nonzero(shifted != -100).view(-1)
-        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        hf = self._hidden_states(input_ids, attention_mask, position_ids, attn_out=attn_out)
+        shifted, inv_count, rows = self._loss_rows(labels.to(self.device), B, S)
+        loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         for s0 in range(0, rows.numel(), 4096):
             r = rows[s0:s0 + 4096]
             logits = ops.gemm_nt(hf.index_select(0, r), self.embed.data)
@@ -998,9 +1009,6 @@ class HipCausalLM(nn.Module):
         split decode attention's buffer the captured step owns (scratch_one: the one-launch attention's).  epoch_advanced: the caller advances the model's step counter
         itself (ops.decode_advance_(epoch=...) behind the step, as the captured loop does); else the step does it here, a launch of its own."""
         c = self.cfg
-        D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.num_key_value_heads
-        QKV = self.qkv
-        scale = 1.0 / math.sqrt(D)
         if pos.dtype == torch.int64 and self.inv_freq.dtype == torch.float32:
             cos, sin = ops.rope_table(pos, self.inv_freq)               # (the four element-wise kernels of _rope_tables in one launch, the same bits)
         else:
@@ -1014,40 +1022,41 @@ class HipCausalLM(nn.Module):
             sync = self._decode_epoch(x.device)
             if not epoch_advanced:
                 sync.add_(1)
-        # (opt-in: the fused kernels of csrc/decode.hip are bit-exact but measured no faster than the separate ones at the C5 shape -- 2.20 against 2.14 ms a token; every
-        #  kernel of the step sits on the ~5 us a dependent launch of a replayed graph costs, whatever it fuses: profiles/r05/README.md)
-        if getattr(self, "decode_fused", False) and not self.training and ops.decode_fusable(x.shape[0], c.hidden_size, Hq, Hkv, D):
-            return self._decode_layers_fused(x, cos, sin, mask, caches, n if n_dev is None else n_dev)
+        nn = n if n_dev is None else n_dev
+        if self.decode_fused and not self.training and ops.decode_fusable(x.shape[0], c.hidden_size, c.num_attention_heads, c.num_key_value_heads, c.head_dim):
+            return self._decode_layers_fused(x, cos, sin, mask, caches, nn)
+
+        def attend(i, qkv):                                             # qkv [B, QKV]
+            return self._decode_attend(qkv, cos, sin, caches[i], mask, nn, scratch, scratch_one, one=self.decode_attn_one)
+
         for i in range(c.num_hidden_layers):
-            if self.lora is not None and not self.training:             # adapters: the norm kernel forms the site's t = scale * h A^T on its way out
-                site = self.lora[i]["qkv"]
-                h1, _, x, t1 = ops.rmsnorm_fwd(x, self.ln1[i].data, c.rms_norm_eps, residual=delta, gemma=self.gemma, lora=(site.A.data, site.scale))
-            else:
-                (h1, _, x), t1 = ops.rmsnorm_fwd(x, self.ln1[i].data, c.rms_norm_eps, residual=delta, gemma=self.gemma), None
-            qkv, _ = self._proj(i, "qkv", h1, self.wqkv[i].data, t_pre=t1)         # [B, QKV]
-            ns = ops.decode_splits(caches[i].shape[1], qkv.shape[0], Hq)
-            nn = n if n_dev is None else n_dev
-            if self.decode_attn_one and ops.decode_one_ok(qkv.shape[0], Hq, D, ns, caches[i].shape[1]):
-                # round 6: RoPE + cache append + scores + values + combine in ONE launch (the bits of the four: tests/test_gpu_decode_fused.py)
-                ao = ops.attn_decode_one(qkv, cos, sin, caches[i], mask, nn, Hq, Hkv, D, scale, ns, scratch=scratch_one if n_dev is not None else None)
-            else:
-                ops.rope_append_(qkv, cos, sin, Hq, Hkv, D, caches[i], nn)   # RoPE on q and k, the rotated k and v into the cache: one launch
-                if ns > 1:
-                    ao = ops.attn_decode_split(qkv, caches[i], mask, nn, Hq, Hkv, D, scale, ns, scratch=scratch if n_dev is not None else None)
-                elif n_dev is None:
-                    ao = ops.attn_decode(qkv, caches[i], mask, n, Hq, Hkv, D, scale)
-                else:
-                    ao = ops.attn_decode_dyn(qkv, caches[i], mask, n_dev, Hq, Hkv, D, scale)
-            attn_delta, _ = self._proj(i, "o", ao, self.wo[i].data, sync=sync)
-            if self.lora is not None and not self.training:             # (the gate|up site's t on the norm's way out too: one launch less a layer, the same bits)
-                site = self.lora[i]["gu"]
-                h2, _, x, t2 = ops.rmsnorm_fwd(x, self.ln2[i].data, c.rms_norm_eps, residual=attn_delta, gemma=self.gemma, lora=(site.A.data, site.scale))
-            else:
-                (h2, _, x), t2 = ops.rmsnorm_fwd(x, self.ln2[i].data, c.rms_norm_eps, residual=attn_delta, gemma=self.gemma), None
-            _, hm, _ = self._proj_glu(i, h2, keep_gu=False, t_pre=t2)
-            delta, _ = self._proj(i, "down", hm, self.wdown[i].data, sync=sync)
+            x, delta = self._layer_infer(i, x, delta, attend, norm_t=("qkv", "gu"), sync=sync)     # adapters: both norms form their site's t (_hidden_states: gate|up only)
         hf, _, _ = ops.rmsnorm_fwd(x, self.norm.data, c.rms_norm_eps, residual=delta, gemma=self.gemma)
         return hf
+
+    def _attend_cached(self, qkv, cache, mask, n, ns, scratch=None):
+        """Attention of one new token per sequence over a cache that already holds its k and v in row n - 1: one workgroup a head for short caches, split over ns workgroups
+        for long ones.  n: an int, or the int32[1] device tensor of a captured step, which then owns `scratch`."""
+        c = self.cfg
+        D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.num_key_value_heads
+        scale, dyn = 1.0 / math.sqrt(D), torch.is_tensor(n)
+        if ns > 1:
+            return ops.attn_decode_split(qkv, cache, mask, n, Hq, Hkv, D, scale, ns, scratch=scratch if dyn else None)
+        if dyn:
+            return ops.attn_decode_dyn(qkv, cache, mask, n, Hq, Hkv, D, scale)
+        return ops.attn_decode(qkv, cache, mask, n, Hq, Hkv, D, scale)
+
+    def _decode_attend(self, qkv, cos, sin, cache, mask, n, scratch=None, scratch_one=None, one=False):
+        """A decode step's RoPE on q and k, the append of the rotated k and of v at cache row n - 1, and the attention.  The split count comes from the cache's CAPACITY
+        (ops.decode_splits: the same in the eager loop and the replayed graph).  n, scratch: as _attend_cached; scratch_one: the one-launch kernel's."""
+        c = self.cfg
+        D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.num_key_value_heads
+        ns = ops.decode_splits(cache.shape[1], qkv.shape[0], Hq)
+        if one and ops.decode_one_ok(qkv.shape[0], Hq, D, ns, cache.shape[1]):
+            # round 6: RoPE + cache append + scores + values + combine in ONE launch (the bits of the four: tests/test_gpu_decode_fused.py)
+            return ops.attn_decode_one(qkv, cos, sin, cache, mask, n, Hq, Hkv, D, 1.0 / math.sqrt(D), ns, scratch=scratch_one if torch.is_tensor(n) else None)
+        ops.rope_append_(qkv, cos, sin, Hq, Hkv, D, cache, n)           # RoPE on q and k, the rotated k and v into the cache: one launch
+        return self._attend_cached(qkv, cache, mask, n, ns, scratch)
 
     def _decode_epoch(self, dev):
         """The decode steps' counter (int32[1] on the device, 1 at first, + 1 every step for the model's lifetime)."""
@@ -1064,10 +1073,7 @@ class HipCausalLM(nn.Module):
         D, Hq, Hkv = c.head_dim, c.num_attention_heads, c.num_key_value_heads
         B, cap = x.shape[0], caches[0].shape[1]
         scale = 1.0 / math.sqrt(D)
-        # attention: round 4's kernels (RoPE + append, scores, values, combine) unless `decode_fused_attn` is set -- the two-launch form of csrc/decode.hip is bit-exact
-        # and reads a KV group's keys once, but measured SLOWER at the C5 shape (82 against 25 us a layer: profiles/r05/README.md); kept for the record and the tests
-        fused_attn = bool(getattr(self, "decode_fused_attn", False))
-        dyn = torch.is_tensor(n)
+        fused_attn = bool(self.decode_fused_attn)
         ns, ns4 = ops.decode_attn_splits(cap), ops.decode_splits(cap, B, Hq)
         pool = self.__dict__.setdefault("_dec_scratch", {})
         key = (B, cap, ns, ns4, fused_attn)
@@ -1086,25 +1092,19 @@ class HipCausalLM(nn.Module):
             if L is None:
                 qkv, x = ops.decode_norm_gemv(x, delta, self.ln1[i].data, c.rms_norm_eps, self.gemma, self.wqkv[i].data)
             else:   # (with adapters: the norm + LoRA-down kernel, then the projection with t given -- redone by each of the projection's workgroups the 48 rows of A cost more than the launch)
-                h1, _, x, t1 = ops.rmsnorm_fwd(x, self.ln1[i].data, c.rms_norm_eps, residual=delta, gemma=self.gemma, lora=(L["qkv"].A.data, L["qkv"].scale))
+                h1, x, t1 = self._norm(i, "qkv", x, delta, True)
                 qkv = ops.decode_gemv(h1, self.wqkv[i].data, lora=site("qkv"), t=t1)
             if fused_attn:
                 ao = ops.decode_attn(qkv, cos, sin, caches[i], mask, n, Hq, Hkv, D, scale, ns, scratch)
-            else:   # RoPE + append, then the attention kernels of round 4 (one workgroup a head for short caches, split over workgroups for long ones)
-                ops.rope_append_(qkv, cos, sin, Hq, Hkv, D, caches[i], n)
-                if ns4 > 1:
-                    ao = ops.attn_decode_split(qkv, caches[i], mask, n, Hq, Hkv, D, scale, ns4, scratch=scratch4 if dyn else None)
-                elif dyn:
-                    ao = ops.attn_decode_dyn(qkv, caches[i], mask, n, Hq, Hkv, D, scale)
-                else:
-                    ao = ops.attn_decode(qkv, caches[i], mask, n, Hq, Hkv, D, scale)
+            else:   # RoPE + append, then the attention kernels of round 4 (never the one-launch form here)
+                ao = self._decode_attend(qkv, cos, sin, caches[i], mask, n, scratch4)
             attn_delta = ops.decode_gemv(ao, self.wo[i].data, lora=site("o"))
             if L is None:
                 hm, x = ops.decode_norm_gemv(x, attn_delta, self.ln2[i].data, c.rms_norm_eps, self.gemma, self.wgu[i].data, glu=glu)
                 delta = ops.decode_gemv(hm, self.wdown[i].data)
             else:
                 # (with adapters the gate|up site keeps the norm + LoRA-down kernel: redone by each of the projection's 2 000 workgroups, A's 32 rows would be read 2 000 times)
-                h2, _, x, t2 = ops.rmsnorm_fwd(x, self.ln2[i].data, c.rms_norm_eps, residual=attn_delta, gemma=self.gemma, lora=(L["gu"].A.data, L["gu"].scale))
+                h2, x, t2 = self._norm(i, "gu", x, attn_delta, True)
                 _, hm, _ = self._proj_glu(i, h2, keep_gu=False, t_pre=t2)
                 sd = L["down"]
                 delta = ops.decode_gemv(hm, self.wdown[i].data, lora=site("down"), t=ops.decode_lora_t(hm, sd.A.data, 16 * sd.n_sub, sd.scale))
@@ -1152,24 +1152,27 @@ class HipCausalLM(nn.Module):
         """merge_adapters=True (opt-in, LoRA models only): the adapters are folded into copies of the projection weights once per call and the decode step runs
         without the five adapter branches per layer -- peft's `merge_and_unload()` for inference.  Not bit-identical to the unmerged step (see `_merged_weights`);
         the reference's own eval loop (ecg_byte/runners/inference.py, main.py:181-195) generates with the adapters unmerged, which stays the default."""
-        if merge_adapters and self.lora is not None:
-            merged = self._merged_weights()
-            params = {"qkv": self.wqkv, "o": self.wo, "gu": self.wgu, "down": self.wdown}
-            saved_lora, saved = self.lora, {k: [w.data for w in ws] for k, ws in params.items()}
-            try:
-                self.lora = None
-                for k, ws in params.items():
-                    for w, mw in zip(ws, merged[k]):
-                        w.data = mw
-                return self._generate(input_ids, attention_mask, max_new_tokens, pad_token_id, eos_token_id, use_cache, return_logits, use_graph, do_sample,
-                                      temperature, top_k, top_p, generator)
-            finally:
-                self.lora = saved_lora
-                for k, ws in params.items():
-                    for w, d in zip(ws, saved[k]):
-                        w.data = d
-        return self._generate(input_ids, attention_mask, max_new_tokens, pad_token_id, eos_token_id, use_cache, return_logits, use_graph, do_sample,
-                              temperature, top_k, top_p, generator)
+        with self._adapters_merged() if merge_adapters and self.lora is not None else contextlib.nullcontext():
+            return self._generate(input_ids, attention_mask, max_new_tokens, pad_token_id, eos_token_id, use_cache, return_logits, use_graph, do_sample,
+                                  temperature, top_k, top_p, generator)
+
+    @contextlib.contextmanager
+    def _adapters_merged(self):
+        """Inside: the model without adapters, its projection weights pointing at `_merged_weights()`; on the way out, as it was."""
+        merged = self._merged_weights()
+        params = {"qkv": self.wqkv, "o": self.wo, "gu": self.wgu, "down": self.wdown}
+        saved_lora, saved = self.lora, {k: [w.data for w in ws] for k, ws in params.items()}
+        try:
+            self.lora = None
+            for k, ws in params.items():
+                for w, mw in zip(ws, merged[k]):
+                    w.data = mw
+            yield
+        finally:
+            self.lora = saved_lora
+            for k, ws in params.items():
+                for w, d in zip(ws, saved[k]):
+                    w.data = d
 
     def _generate(self, input_ids=None, attention_mask=None, max_new_tokens=128, pad_token_id=None, eos_token_id=None,
                   use_cache=True, return_logits=False, use_graph=None, do_sample=None, temperature=None, top_k=None, top_p=None,

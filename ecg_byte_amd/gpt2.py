@@ -203,29 +203,11 @@ class HipGPT2LM(HipCausalLM):
         x = ops.embed_fwd(input_ids.view(-1), self.embed.data, 1.0)
         return ops.add(x, ops.embed_fwd(position_ids.reshape(-1).contiguous(), self.wpe.data, 1.0), out=x)
 
-    def _prep(self, input_ids, attention_mask, position_ids):
-        dev = self.device
-        ops.require_current(dev)
-        input_ids = input_ids.to(dev).contiguous()
-        B, S = input_ids.shape
-        mask = (attention_mask.to(dev).float() if attention_mask is not None else torch.ones(B, S, device=dev)).contiguous()
-        if position_ids is None:
-            position_ids = torch.arange(S, device=dev)[None].expand(B, S)
-        return input_ids, mask, position_ids.to(dev).long(), B, S
-
     def _forward_loss(self, input_ids, attention_mask, labels, position_ids):
         c = self.cfg
-        H, nh, D, eps = c.n_embd, c.n_head, c.head_dim, c.layer_norm_epsilon
-        input_ids, mask, position_ids, B, S = self._prep(input_ids, attention_mask, position_ids)
-        labels = labels.to(self.device)
-        if S % 64:   # as HipCausalLM._forward_loss: masked, unlabelled positions on the left change nothing
-            lpad = 64 - S % 64
-            dev = self.device
-            input_ids = torch.cat([torch.zeros((B, lpad), dtype=input_ids.dtype, device=dev), input_ids], 1).contiguous()
-            mask = torch.cat([torch.zeros((B, lpad), device=dev), mask], 1).contiguous()
-            position_ids = torch.cat([torch.zeros((B, lpad), dtype=position_ids.dtype, device=dev), position_ids], 1)
-            labels = torch.cat([torch.full((B, lpad), -100, dtype=labels.dtype, device=dev), labels], 1)
-            S += lpad
+        nh, D, eps = c.n_head, c.head_dim, c.layer_norm_epsilon
+        input_ids, mask, position_ids, labels, B, S, _ = self._prep(input_ids, attention_mask, position_ids, labels, pad=True)
+        position_ids = position_ids.long()
         scale = 1.0 / math.sqrt(D)
         x = self._embed(input_ids, position_ids)
         x, seed_e = self._drop(x, c.embd_pdrop, 1)
@@ -253,12 +235,6 @@ class HipGPT2LM(HipCausalLM):
         loss, dhf = self._loss_head(hf, labels, B, S)
         self._saved = (saved, input_ids, position_ids, mask, (xf, muf, rsf), dhf, (B, S), seed_e)
         return loss.squeeze(0)
-
-    def _backward(self, grad_out):
-        if self.grad_sync is not None and hasattr(self.grad_sync, "backward_kernels"):
-            with self.grad_sync.backward_kernels():     # one-tile input-gradient GEMMs only while a gradient exchange can be in flight
-                return self._backward_impl(grad_out)
-        return self._backward_impl(grad_out)
 
     def _backward_impl(self, grad_out):
         c = self.cfg
@@ -337,10 +313,13 @@ class HipGPT2LM(HipCausalLM):
         hm = ops.bias_gelu_new_(ops.gemm_nt(h2, self.wfc[i].data), self.bfc[i].data)
         return x, ops.bias_(ops.gemm_nt(hm, self.wproj[i].data), self.bproj[i].data)
 
-    def _hidden_states(self, input_ids, attention_mask=None, position_ids=None, kv_out=None):
+    def _hidden_states(self, input_ids, attention_mask=None, position_ids=None, kv_out=None, attn_out=None):
+        if attn_out is not None:
+            raise NotImplementedError("attention probabilities are built for the Llama / Gemma blocks only")
         c = self.cfg
         H, nh, D = c.n_embd, c.n_head, c.head_dim
-        input_ids, mask, position_ids, B, S = self._prep(input_ids, attention_mask, position_ids)
+        input_ids, mask, position_ids, _, B, S, _ = self._prep(input_ids, attention_mask, position_ids)
+        position_ids = position_ids.long()
         scale = 1.0 / math.sqrt(D)
 
         def attend(i, qkv):
@@ -355,20 +334,15 @@ class HipGPT2LM(HipCausalLM):
 
     def _decode_step(self, tokens, pos, mask, caches, n, n_dev=None, scratch=None):
         c = self.cfg
-        H, nh, D = c.n_embd, c.n_head, c.head_dim
-        scale = 1.0 / math.sqrt(D)
+        H = c.n_embd
 
-        def attend(i, qkv):
-            ns = ops.decode_splits(caches[i].shape[1], qkv.shape[0], nh)      # by the caches' capacity: see HipCausalLM._decode_step
+        def attend(i, qkv):                                                   # no RoPE: k and v go into the cache as they are
+            ns = ops.decode_splits(caches[i].shape[1], qkv.shape[0], c.n_head)   # by the caches' capacity: see HipCausalLM._decode_attend
             if n_dev is None:
                 caches[i][:, n - 1].copy_(qkv[:, H:])
-                if ns > 1:
-                    return ops.attn_decode_split(qkv, caches[i], mask, n, nh, nh, D, scale, ns)
-                return ops.attn_decode(qkv, caches[i], mask, n, nh, nh, D, scale)
-            ops.kv_append(qkv, H, caches[i], n_dev)
-            if ns > 1:
-                return ops.attn_decode_split(qkv, caches[i], mask, n_dev, nh, nh, D, scale, ns, scratch=scratch)
-            return ops.attn_decode_dyn(qkv, caches[i], mask, n_dev, nh, nh, D, scale)
+            else:
+                ops.kv_append(qkv, H, caches[i], n_dev)
+            return self._attend_cached(qkv, caches[i], mask, n if n_dev is None else n_dev, ns, scratch)
 
         x, delta = self._embed(tokens[:, None], pos[:, None]), None
         for i in range(c.n_layer):
