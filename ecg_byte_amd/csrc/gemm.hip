@@ -19,6 +19,7 @@
 #include <string>
 #include <type_traits>
 
+#include "gemm_host.hpp"
 #include "glu_math.hpp"
 #include "tokenizer.hpp"
 
@@ -2019,88 +2020,83 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_cols_kernel(GemmArgs G)
 int g_gemm_group_m = 0;
 int g_gemm_tile = 0;   // 0 auto; 259 = 256x256 phased, one tile per workgroup (no persistent tile loop: A/B); forced: 128 = 128x128 tile, 256 = 256x256 phased on 16x16x32 MFMA (the default for big problems),
                        // 257 = 256x256 on 32x32x16 MFMA, 258 = 256x256 on 16x16x32 with one barrier pair per K-tile (the earlier kernels, kept for A/B)
-// persistent tile loop (gemm_nt_kernel_m16pp): whole interior tiles, no batch, plain bf16 store, at least two rounds of tiles per CU
-int n_cus()
-{
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    }
-    return n;
-}
 // Persistent workgroups own a STATIC share of the tiles and fill every CU: a kernel of another stream that holds CUs while one runs (an RCCL
 // collective under the backward of a data-parallel step) would leave the late-starting workgroups' shares to run after all the others.  The
 // input-gradient GEMMs are the ones that run beside the gradient exchange: ecgb_set_gemm_backward_persistent(0) sends them to the one-tile kernels
 // (parallel.GradAllReduce does so when it is active with more than one rank); the forward GEMMs never overlap a collective.
 int g_nn_persist = 1;
+// persistent tile loop (gemm_nt_kernel_m16pp): whole interior tiles, no batch, plain bf16 store, at least two rounds of tiles per CU
 bool persist_ok(const GemmArgs &G, int batch, bool glu)
 {
     const int KT = G.K / BK + (G.K2 > 0 ? G.K2 / BK : 0);
     const long long tiles = (long long)(G.M / 256) * (G.N / 256);
     // (long contractions gain nothing -- the prologue is 0.5 % of a K = 16 384 tile -- and lose the dynamic dispatch's load balancing: measured +1.5 %)
     return g_gemm_tile != 259 && batch == 1 && !G.inner && G.M % 256 == 0 && G.N % 256 == 0 && KT >= 2 && KT <= 64 && G.accumulate_f32 == 0 && (G.ldc & 7) == 0 &&
-           (!glu || ((G.ldh & 7) == 0 && (G.glu_I & 7) == 0)) && tiles >= 2 * n_cus();
+           (!glu || ((G.ldh & 7) == 0 && (G.glu_I & 7) == 0)) && tiles >= 2 * ecgb::device_cus();
 }
 
+// What every entry point starts from: the first operand pair, the shape and the strides; no batch, no second pair, no epilogue, a plain bf16 store
+GemmArgs gemm_args(const void *a_dev, long long lda, const void *b_dev, long long ldb, void *c_dev, long long ldc, int M, int N, int K, float alpha)
+{
+    GemmArgs G{};
+    G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = c_dev;
+    G.M = M; G.N = N; G.K = K;
+    G.lda = lda; G.ldb = ldb; G.ldc = ldc;
+    G.alpha = alpha;
+    G.div_a = G.div_b = 1;
+    G.group_m = g_gemm_group_m;
+    return G;
+}
 
-int launch_gemm(GemmArgs &G, int batch, hipStream_t stream)
+constexpr int kLds256 = 2 * (256 + 256) * BK * 2;       // dynamic LDS of the 256x256 tile kernels: two stages of both operands' K-tiles
+constexpr int kLds128 = 2 * (128 + 128) * BK * 2;
+using GemmKern = void (*)(GemmArgs);
+
+// NT product on the eight-wave kernels (four waves at the 128x128 tile): decides kernel, tile counts and grid
+int launch_gemm(GemmArgs &G, int batch, void *stream)
 {
     // the 256x256 tile halves L2->LDS traffic per FLOP but needs enough tiles to fill the chip
     const long long tiles256 = (long long)((G.M + 255) / 256) * ((G.N + 255) / 256) * batch;
     const bool big = g_gemm_tile >= 256 || (g_gemm_tile == 0 && tiles256 >= 192 && G.M >= 256 && G.N >= 256);
-    hipError_t e;
+    const int tile = big ? 256 : 128;
+    G.tiles_m = (G.M + tile - 1) / tile; G.tiles_n = (G.N + tile - 1) / tile;
+    dim3 grid((unsigned)(G.tiles_m * G.tiles_n), 1, (unsigned)batch);
+    GemmKern kern;
     if (big && g_gemm_tile != 257 && g_gemm_tile != 258) {
-        constexpr int lds = 2 * (256 + 256) * BK * 2;
-        G.tiles_m = (G.M + 255) / 256; G.tiles_n = (G.N + 255) / 256;
         if (persist_ok(G, batch, false)) {
-            auto kern = G.K2 ? gemm_nt_kernel_m16pp<true, 0> : gemm_nt_kernel_m16pp<false, 0>;
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3((unsigned)n_cus(), 1, 1), dim3(512), lds, stream, G);
+            kern = G.K2 ? gemm_nt_kernel_m16pp<true, 0> : gemm_nt_kernel_m16pp<false, 0>;
+            grid = dim3((unsigned)ecgb::device_cus(), 1, 1);
         } else {
-            auto kern = G.K2 ? gemm_nt_kernel_m16p<256, 256, 2, 4, true> : gemm_nt_kernel_m16p<256, 256, 2, 4>;
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(kern, dim3((unsigned)(G.tiles_m * G.tiles_n), 1, (unsigned)batch), dim3(512), lds, stream, G);
+            kern = G.K2 ? gemm_nt_kernel_m16p<256, 256, 2, 4, true> : gemm_nt_kernel_m16p<256, 256, 2, 4>;
         }
     } else if (big && g_gemm_tile == 258) {
-        constexpr int lds = 2 * (256 + 256) * BK * 2;
-        auto kern = G.K2 ? gemm_nt_kernel_m16<256, 256, 2, 4, true> : gemm_nt_kernel_m16<256, 256, 2, 4>;
-        G.tiles_m = (G.M + 255) / 256; G.tiles_n = (G.N + 255) / 256;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess)
-            hipLaunchKernelGGL(kern, dim3((unsigned)(G.tiles_m * G.tiles_n), 1, (unsigned)batch), dim3(512), lds, stream, G);
+        kern = G.K2 ? gemm_nt_kernel_m16<256, 256, 2, 4, true> : gemm_nt_kernel_m16<256, 256, 2, 4>;
     } else if (big) {
-        constexpr int lds = 2 * (256 + 256) * BK * 2;
-        auto kern = G.K2 ? gemm_nt_kernel<256, 256, 2, 4, true> : gemm_nt_kernel<256, 256, 2, 4>;
-        G.tiles_m = (G.M + 255) / 256; G.tiles_n = (G.N + 255) / 256;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess)
-            hipLaunchKernelGGL(kern, dim3((unsigned)(G.tiles_m * G.tiles_n), 1, (unsigned)batch), dim3(512), lds, stream, G);
+        kern = G.K2 ? gemm_nt_kernel<256, 256, 2, 4, true> : gemm_nt_kernel<256, 256, 2, 4>;
     } else {
-        constexpr int lds = 2 * (128 + 128) * BK * 2;
-        auto kern = G.K2 ? gemm_nt_kernel<128, 128, 2, 2, true> : gemm_nt_kernel<128, 128, 2, 2>;
-        G.tiles_m = (G.M + 127) / 128; G.tiles_n = (G.N + 127) / 128;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess)
-            hipLaunchKernelGGL(kern, dim3((unsigned)(G.tiles_m * G.tiles_n), 1, (unsigned)batch), dim3(256), lds, stream, G);
+        kern = G.K2 ? gemm_nt_kernel<128, 128, 2, 2, true> : gemm_nt_kernel<128, 128, 2, 2>;
     }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nt_kernel: ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-    return ECGB_OK;
+    return ecgb::launch_kernel(kern, grid, dim3(big ? 512 : 256), big ? kLds256 : kLds128, stream, "gemm_nt_kernel", G);
+}
+
+// Few rows (a decode step): bandwidth-bound kernels, a wave per output column.  Long rows and few columns: four waves per column.
+bool skinny_split(int N, int K) { return K >= 8192 && K % 32 == 0 && N <= 8192; }
+
+// The few-row product of ecgb_gemm_nt_bf16 and, with a second pair behind the first in the same launch, of ecgb_gemm_nt_bf16_cat; M <= 8, K % 8 == 0
+int launch_skinny(const GemmArgs &G, void *stream, const char *who)
+{
+    const bool split = skinny_split(G.N, G.K);
+    GemmKern kern;
+    unsigned cols_per_block = split ? 1 : 4;
+    if (G.M <= 2) kern = split ? gemm_nt_skinny_kernel<2, 4> : gemm_nt_skinny_kernel<2, 1>;
+    else if (split) { kern = gemm_nt_skinny_cols_kernel<8, 4, 4>; cols_per_block = 4; }
+    else if (G.N >= 8192) { kern = gemm_nt_skinny_cols_kernel<8, 4, 1>; cols_per_block = 16; }
+    else kern = gemm_nt_skinny_kernel<8, 1>;
+    return ecgb::launch_kernel(kern, dim3(((unsigned)G.N + cols_per_block - 1) / cols_per_block), dim3(256), 0, stream, who, G);
 }
 
 }  // namespace
 
-// csrc/gemm_w4.hip: the four-wave kernel (128x128 wave tiles, one wave per SIMD) for plain NT products of whole 256x256 tiles
-namespace ecgb {
-bool gemm_w4_applies(const void *a_dev, long long lda, const void *b_dev, long long ldb, const void *c_dev, long long ldc, int M, int N, int K);
-bool gemm_w4_span_ok(int lay, long long lda, long long ldb, long long K, long long extra_rows_b);      // 32-bit DMA offsets over the whole contraction (gemm_w4.hip)
-int gemm_w4_launch(const void *a_dev, long long lda, const void *b_dev, long long ldb, void *c_dev, long long ldc, int M, int N, int K, float alpha, void *stream,
-                   int epi, void *h_dev, long long ldh, const void *a2_dev, long long lda2, const void *b2_dev, long long ldb2, int K2,
-                   const float *rope_cos, const float *rope_sin, int rope_cols, int lay, const void *gu_dev = nullptr, long long ldgu = 0,
-                   const void *ldt_dev = nullptr, const void *lat_dev = nullptr, float lscale = 0.f, unsigned lthr = 0, unsigned lseed = 0);
-}
 namespace { int g_gemm_w4 = 1; }
 extern "C" int ecgb_set_gemm_w4(int on)
 {
@@ -2123,6 +2119,25 @@ extern "C" int ecgb_set_gemm_backward_persistent(int on)
 
 extern "C" int ecgb_get_gemm_backward_persistent(void) { return g_nn_persist; }
 
+namespace {
+// Does the four-wave kernel (gemm_w4.hip) take this product?  The three A/B switches -- it is on, no eight-wave tile is forced, and for the persistent NN / TN forms
+// no gradient exchange may hold CUs (g_nn_persist, see above) --, its 32-bit DMA span over the contraction, and whole tiles with its share of K-tiles per CU.
+// M, N, K: the product's own (TN: C [M, N] over K contraction rows, both operands bounded by the span alone).
+bool w4_takes(int lay, const void *a_dev, long long lda, const void *b_dev, long long ldb, const void *c_dev, long long ldc, int M, int N, int K, long long extra_rows_b = 0)
+{
+    if (!g_gemm_w4 || g_gemm_tile != 0 || (lay != ecgb::W4_NT && !g_nn_persist) || !ecgb::gemm_w4_span_ok(lay, lda, ldb, K, extra_rows_b)) return false;
+    return lay == ecgb::W4_TN ? ecgb::gemm_w4_applies(a_dev, 8, b_dev, 8, c_dev, ldc, M, N, K) : ecgb::gemm_w4_applies(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K);
+}
+
+// The LoRA epilogues' dropout, as ecgb_lora_down / ecgb_lora_dx fill it (lora.hip): 16-bit threshold, the scale of the kept elements, the 32-bit seed
+void w4_lora_dropout(ecgb::W4Launch &L, float scale, float p, uint64_t seed)
+{
+    L.lthr = (unsigned)(p * 65536.0f);
+    L.lscale = scale / (1.0f - (float)L.lthr / 65536.0f);
+    L.lseed = (unsigned)(seed ^ (seed >> 32));
+}
+}  // namespace
+
 extern "C" int ecgb_set_gemm_tile(int tile)
 {
     if (tile != 0 && tile != 128 && (tile < 256 || tile > 259)) { ecgb::set_error("ecgb_set_gemm_tile: 0, 128, 256, 257, 258 or 259"); return ECGB_ERR_INVALID; }
@@ -2142,33 +2157,14 @@ extern "C" int ecgb_gemm_nt_bf16(const void *a_dev, long long lda, const void *b
         ecgb::set_error("ecgb_gemm_nt_bf16: K must be a multiple of 64 and operands 16-byte aligned with strides % 8 == 0");
         return ECGB_ERR_UNSUPPORTED;
     }
-    GemmArgs G{};
-    G.group_m = g_gemm_group_m;
-    G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = c_dev;
-    G.M = M; G.N = N; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = ldc;
+    GemmArgs G = gemm_args(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha);
     G.batch_a = batch_a; G.batch_b = batch_b; G.batch_c = batch_c;
-    G.accumulate_f32 = accumulate_f32; G.alpha = alpha;
-    G.A2 = G.B2 = nullptr; G.lda2 = G.ldb2 = 0; G.K2 = 0;
-    G.inner = 0; G.outer_a = G.inner_a = G.outer_b = G.inner_b = G.outer_c = G.inner_c = 0; G.div_a = G.div_b = 1;
-    if (M <= 8 && batch == 1 && K % 8 == 0) {   // a few rows: bandwidth-bound column-per-wave kernel (ecgb_gemm_nt_bf16_cat has the same dispatch)
-        const bool split = (K >= 8192 && K % 32 == 0 && N <= 8192);      // long rows, few columns: four waves per column
-        const dim3 grid(split ? (unsigned)N : (unsigned)((N + 3) / 4));
-        if (M <= 2) {
-            if (split) hipLaunchKernelGGL((gemm_nt_skinny_kernel<2, 4>), grid, dim3(256), 0, (hipStream_t)stream, G);
-            else hipLaunchKernelGGL((gemm_nt_skinny_kernel<2, 1>), grid, dim3(256), 0, (hipStream_t)stream, G);
-        } else {
-            if (split) hipLaunchKernelGGL((gemm_nt_skinny_cols_kernel<8, 4, 4>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, G);
-            else if (N >= 8192) hipLaunchKernelGGL((gemm_nt_skinny_cols_kernel<8, 4, 1>), dim3((unsigned)((N + 15) / 16)), dim3(256), 0, (hipStream_t)stream, G);
-            else hipLaunchKernelGGL((gemm_nt_skinny_kernel<8, 1>), grid, dim3(256), 0, (hipStream_t)stream, G);
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nt_skinny_kernel: ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-        return ECGB_OK;
-    }
+    G.accumulate_f32 = accumulate_f32;
+    if (M <= 8 && batch == 1 && K % 8 == 0) return launch_skinny(G, stream, "ecgb_gemm_nt_bf16");
     // whole 256x256 tiles, plain bf16 store, one problem, at least two tiles per CU: the four-wave kernel (the same bits; 1-6 % faster on the step's forward shapes)
-    if (g_gemm_w4 && g_gemm_tile == 0 && batch == 1 && accumulate_f32 == 0 && ecgb::gemm_w4_span_ok(0, lda, ldb, K, 0) && ecgb::gemm_w4_applies(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K))
-        return ecgb::gemm_w4_launch(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, 0, 0);
-    return launch_gemm(G, batch, (hipStream_t)stream);
+    if (batch == 1 && accumulate_f32 == 0 && w4_takes(ecgb::W4_NT, a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K))
+        return ecgb::gemm_w4_launch(ecgb::W4Launch{a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream});
+    return launch_gemm(G, batch, stream);
 }
 
 extern "C" int ecgb_gemm_nt_bf16_cat(const void *a_dev, long long lda, const void *b_dev, long long ldb, const void *a2_dev, long long lda2,
@@ -2183,33 +2179,16 @@ extern "C" int ecgb_gemm_nt_bf16_cat(const void *a_dev, long long lda, const voi
         ecgb::set_error("ecgb_gemm_nt_bf16_cat: K and K2 must be multiples of 64 and operands 16-byte aligned with strides % 8 == 0");
         return ECGB_ERR_UNSUPPORTED;
     }
-    GemmArgs G{};
-    G.group_m = g_gemm_group_m;
-    G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = c_dev;
-    G.M = M; G.N = N; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = ldc;
-    G.batch_a = G.batch_b = G.batch_c = 0;
-    G.accumulate_f32 = accumulate_f32; G.alpha = alpha;
+    GemmArgs G = gemm_args(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha);
     G.A2 = (const unsigned short *)a2_dev; G.B2 = (const unsigned short *)b2_dev; G.lda2 = lda2; G.ldb2 = ldb2; G.K2 = K2;
-    G.inner = 0; G.outer_a = G.inner_a = G.outer_b = G.inner_b = G.outer_c = G.inner_c = 0; G.div_a = G.div_b = 1;
-    if (M <= 8) {   // a few rows (a decode step with adapters): the column-per-wave kernels take the second pair behind the first, one launch
-        const bool split = (K >= 8192 && K % 32 == 0 && N <= 8192);
-        const dim3 grid(split ? (unsigned)N : (unsigned)((N + 3) / 4));
-        if (M <= 2) {
-            if (split) hipLaunchKernelGGL((gemm_nt_skinny_kernel<2, 4>), grid, dim3(256), 0, (hipStream_t)stream, G);
-            else hipLaunchKernelGGL((gemm_nt_skinny_kernel<2, 1>), grid, dim3(256), 0, (hipStream_t)stream, G);
-        } else {
-            if (split) hipLaunchKernelGGL((gemm_nt_skinny_cols_kernel<8, 4, 4>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, G);
-            else if (N >= 8192) hipLaunchKernelGGL((gemm_nt_skinny_cols_kernel<8, 4, 1>), dim3((unsigned)((N + 15) / 16)), dim3(256), 0, (hipStream_t)stream, G);
-            else hipLaunchKernelGGL((gemm_nt_skinny_kernel<8, 1>), grid, dim3(256), 0, (hipStream_t)stream, G);
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nt_skinny_kernel (cat): ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-        return ECGB_OK;
+    G.accumulate_f32 = accumulate_f32;
+    if (M <= 8) return launch_skinny(G, stream, "ecgb_gemm_nt_bf16_cat");      // (a decode step with adapters: one launch for both pairs)
+    if (accumulate_f32 == 0 && ecgb::gemm_w4_span_ok(0, lda2, ldb2, K2, 0) && w4_takes(ecgb::W4_NT, a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K)) {
+        ecgb::W4Launch L{a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream};
+        L.a2 = a2_dev; L.lda2 = lda2; L.b2 = b2_dev; L.ldb2 = ldb2; L.K2 = K2;
+        return ecgb::gemm_w4_launch(L);
     }
-    if (g_gemm_w4 && g_gemm_tile == 0 && accumulate_f32 == 0 && ecgb::gemm_w4_span_ok(0, lda2, ldb2, K2, 0) && ecgb::gemm_w4_span_ok(0, lda, ldb, K, 0) &&
-        ecgb::gemm_w4_applies(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K))
-        return ecgb::gemm_w4_launch(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream, 0, nullptr, 0, a2_dev, lda2, b2_dev, ldb2, K2, nullptr, nullptr, 0, 0);
-    return launch_gemm(G, 1, (hipStream_t)stream);
+    return launch_gemm(G, 1, stream);
 }
 
 // One launch for a decode step's adapter site (o, down): t = t_scale * x A_lora^T by the launch's first workgroups (into t64_dev: [M, K2] 64-bit words, an element's bf16 bits
@@ -2228,21 +2207,18 @@ extern "C" int ecgb_gemm_nt_bf16_lora_decode(const void *x_dev, long long ldx, c
         ecgb::set_error("ecgb_gemm_nt_bf16_lora_decode: one or two rows, K a multiple of 64, K2 <= 64, operands 16-byte aligned with strides % 8 == 0");
         return ECGB_ERR_UNSUPPORTED;
     }
-    const bool split = (K >= 8192 && K % 32 == 0 && N <= 8192);            // (ecgb_gemm_nt_bf16's rule; K2 <= 8192 always: both products take the same kernel form)
-    if (split != (K >= 8192 && K % 32 == 0)) { ecgb::set_error("ecgb_gemm_nt_bf16_lora_decode: the two products would take different kernels"); return ECGB_ERR_UNSUPPORTED; }
-    GemmArgs G{}, P{};
-    G.A = (const unsigned short *)x_dev; G.B = (const unsigned short *)w_dev; G.C = y_dev;
-    G.M = M; G.N = N; G.K = K; G.lda = ldx; G.ldb = ldw; G.ldc = ldy; G.accumulate_f32 = 0; G.alpha = 1.f;
-    G.A2 = nullptr; G.B2 = (const unsigned short *)b_lora_dev; G.lda2 = 0; G.ldb2 = ldb_lora; G.K2 = K2; G.div_a = G.div_b = 1;      // (A2: the words of t64_dev)
-    P.A = (const unsigned short *)x_dev; P.B = (const unsigned short *)a_lora_dev; P.C = t64_dev;
-    P.M = M; P.N = K2; P.K = K; P.lda = ldx; P.ldb = lda_lora; P.ldc = K2; P.accumulate_f32 = 0; P.alpha = t_scale; P.K2 = 0; P.div_a = P.div_b = 1;
-    SkinnySync Y{t64_dev, epoch_dev, split ? K2 : (K2 + 3) / 4};
+    const bool split = skinny_split(N, K);
+    if (split != skinny_split(K2, K)) {             // both products must take the same kernel form
+        ecgb::set_error("ecgb_gemm_nt_bf16_lora_decode: the two products would take different kernels");
+        return ECGB_ERR_UNSUPPORTED;
+    }
+    GemmArgs G = gemm_args(x_dev, ldx, w_dev, ldw, y_dev, ldy, M, N, K, 1.f);
+    G.B2 = (const unsigned short *)b_lora_dev; G.ldb2 = ldb_lora; G.K2 = K2;      // (A2: the words of t64_dev)
+    const GemmArgs P = gemm_args(x_dev, ldx, a_lora_dev, lda_lora, t64_dev, K2, M, K2, K, t_scale);
+    const SkinnySync Y{t64_dev, epoch_dev, split ? K2 : (K2 + 3) / 4};
     const dim3 grid((unsigned)Y.pre_blocks + (split ? (unsigned)N : (unsigned)((N + 3) / 4)));
-    if (split) hipLaunchKernelGGL((gemm_nt_skinny_lora_kernel<2, 4>), grid, dim3(256), 0, (hipStream_t)stream, G, P, Y);
-    else hipLaunchKernelGGL((gemm_nt_skinny_lora_kernel<2, 1>), grid, dim3(256), 0, (hipStream_t)stream, G, P, Y);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nt_skinny_lora_kernel: ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-    return ECGB_OK;
+    auto kern = split ? gemm_nt_skinny_lora_kernel<2, 4> : gemm_nt_skinny_lora_kernel<2, 1>;
+    return ecgb::launch_kernel(kern, grid, dim3(256), 0, stream, "ecgb_gemm_nt_bf16_lora_decode", G, P, Y);
 }
 
 extern "C" int ecgb_gemm_nt_bf16_heads(const void *a_dev, long long lda, const void *b_dev, long long ldb, void *c_dev,
@@ -2259,16 +2235,11 @@ extern "C" int ecgb_gemm_nt_bf16_heads(const void *a_dev, long long lda, const v
         ecgb::set_error("ecgb_gemm_nt_bf16_heads: K must be a multiple of 64 and every operand offset 16-byte aligned");
         return ECGB_ERR_UNSUPPORTED;
     }
-    GemmArgs G{};
-    G.group_m = g_gemm_group_m;
-    G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = c_dev;
-    G.M = M; G.N = N; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = ldc;
-    G.batch_a = G.batch_b = G.batch_c = 0;
-    G.accumulate_f32 = accumulate_f32; G.alpha = alpha;
-    G.A2 = G.B2 = nullptr; G.lda2 = G.ldb2 = 0; G.K2 = 0;
+    GemmArgs G = gemm_args(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha);
+    G.accumulate_f32 = accumulate_f32;
     G.inner = inner; G.outer_a = outer_a; G.inner_a = inner_a; G.div_a = div_a;
     G.outer_b = outer_b; G.inner_b = inner_b; G.div_b = div_b; G.outer_c = outer_c; G.inner_c = inner_c;
-    return launch_gemm(G, batch, (hipStream_t)stream);
+    return launch_gemm(G, batch, stream);
 }
 
 // dW-style product: C[N,K] (bf16, row stride ldc) = alpha * A^T . B, A = [M,N] row-major (lda), B = [M,K] row-major (ldb).
@@ -2281,13 +2252,6 @@ extern "C" int ecgb_gemm_tn_bf16(const void *a_dev, long long lda, const void *b
         ecgb::set_error("ecgb_gemm_tn_bf16: M % 64, N % 8, K % 8, 16-byte aligned operands required");
         return ECGB_ERR_UNSUPPORTED;
     }
-    GemmArgs G{};
-    G.group_m = g_gemm_group_m;
-    G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = c_dev;
-    G.M = M; G.N = N; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = ldc;
-    G.batch_a = G.batch_b = G.batch_c = 0;
-    G.A2 = G.B2 = nullptr; G.lda2 = G.ldb2 = 0; G.K2 = 0;
-    G.tiles_m = (N + 255) / 256; G.tiles_n = (K + 255) / 256;
     if (splits < 1 || splits > 64) { ecgb::set_error("ecgb_gemm_tn_bf16: splits must be 1..64"); return ECGB_ERR_INVALID; }
     if ((64 * lda + N) * 2 >= (1ll << 32) || (64 * ldb + K) * 2 >= (1ll << 32)) {      // per-lane byte offsets inside a K-tile are 32-bit
         ecgb::set_error("ecgb_gemm_tn_bf16: row strides above 2^24 elements are not supported");
@@ -2295,21 +2259,17 @@ extern "C" int ecgb_gemm_tn_bf16(const void *a_dev, long long lda, const void *b
     }
     // one K-slice, whole tiles, a long contraction: the four-wave kernel on the TN layout (the same bits; dW of the down projection 0.836 -> 0.785 ms, of gate|up 1.589 -> 1.574);
     // persistent, so not while a gradient exchange may hold CUs (g_nn_persist)
-    if (splits == 1 && g_gemm_w4 && g_nn_persist && g_gemm_tile == 0 && N % 256 == 0 && K % 256 == 0 && (ldc & 7) == 0 && ((uintptr_t)c_dev & 15) == 0 &&
-        ecgb::gemm_w4_span_ok(2, lda, ldb, M, 0) && ecgb::gemm_w4_applies(a_dev, 8, b_dev, 8, c_dev, ldc, N, K, M))
-        return ecgb::gemm_w4_launch(a_dev, lda, b_dev, ldb, c_dev, ldc, N, K, M, alpha, stream, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, 0, 2);
-    G.accumulate_f32 = splits > 1 ? 1 : 0; G.alpha = alpha;      // splits > 1: c_dev is fp32 [splits][N, ldc], one slab per K-slice
-    G.split_stride = (long long)N * ldc;
-    G.inner = 0; G.outer_a = G.inner_a = G.outer_b = G.inner_b = G.outer_c = G.inner_c = 0; G.div_a = G.div_b = 1;
-    constexpr int lds = 2 * (256 + 256) * 64 * 2;
-    auto kern = (g_gemm_tile == 258) ? gemm_tn_kernel_m16<256, 256, 2, 4> : gemm_tn_kernel_tr<256, 256, 2, 4>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)(G.tiles_m * G.tiles_n), (unsigned)splits), dim3(512), lds, (hipStream_t)stream, G);
-        e = hipGetLastError();
+    if (splits == 1 && N % 256 == 0 && K % 256 == 0 && (ldc & 7) == 0 && ((uintptr_t)c_dev & 15) == 0 && w4_takes(ecgb::W4_TN, a_dev, lda, b_dev, ldb, c_dev, ldc, N, K, M)) {
+        ecgb::W4Launch L{a_dev, lda, b_dev, ldb, c_dev, ldc, N, K, M, alpha, stream};
+        L.layout = ecgb::W4_TN;
+        return ecgb::gemm_w4_launch(L);
     }
-    if (e != hipSuccess) { ecgb::set_error(std::string("gemm_tn_kernel: ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-    return ECGB_OK;
+    GemmArgs G = gemm_args(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha);
+    G.tiles_m = (N + 255) / 256; G.tiles_n = (K + 255) / 256;
+    G.accumulate_f32 = splits > 1 ? 1 : 0;      // splits > 1: c_dev is fp32 [splits][N, ldc], one slab per K-slice
+    G.split_stride = (long long)N * ldc;
+    auto kern = (g_gemm_tile == 258) ? gemm_tn_kernel_m16<256, 256, 2, 4> : gemm_tn_kernel_tr<256, 256, 2, 4>;
+    return ecgb::launch_kernel(kern, dim3((unsigned)(G.tiles_m * G.tiles_n), (unsigned)splits), dim3(512), kLds256, stream, "gemm_tn_kernel", G);
 }
 
 // H[M, I] = act(gate) * up with gate | up = alpha * (A . B^T [+ A2 . B2^T]),  B = [2 I, K] (gate rows, then up rows): the gate|up
@@ -2329,57 +2289,33 @@ extern "C" int ecgb_gemm_nt_glu_bf16(const void *a_dev, long long lda, const voi
         ecgb::set_error("ecgb_gemm_nt_glu_bf16: K % 64, inter % 128, 16-byte aligned operands, strides % 8 (outputs % 4) required");
         return ECGB_ERR_UNSUPPORTED;
     }
+    GemmArgs G = gemm_args(a_dev, lda, b_dev, ldb, c_dev, ldc, M, 2 * inter, K, alpha);
+    G.A2 = (const unsigned short *)a2_dev; G.B2 = (const unsigned short *)b2_dev; G.lda2 = lda2; G.ldb2 = ldb2; G.K2 = K2 > 0 ? K2 : 0;
+    G.H = (unsigned short *)h_dev; G.ldh = ldh; G.glu_I = inter;
     if (M <= 8 && K % 8 == 0 && (K2 <= 0 || K2 % 8 == 0)) {       // a decode step: the few-row kernel with the GLU folded in (bound by reading the two weight rows once)
-        GemmArgs G{};
-        G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = c_dev;
-        G.M = M; G.N = 2 * inter; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = ldc; G.alpha = alpha;
-        G.A2 = (const unsigned short *)a2_dev; G.B2 = (const unsigned short *)b2_dev; G.lda2 = lda2; G.ldb2 = ldb2; G.K2 = K2 > 0 ? K2 : 0;
-        G.H = (unsigned short *)h_dev; G.ldh = ldh; G.glu_I = inter;
-        const dim3 grid((unsigned)((inter + 3) / 4));
-        if (M <= 2) {
-            if (gelu_tanh) hipLaunchKernelGGL((gemm_nt_skinny_glu_kernel<2, 2>), grid, dim3(256), 0, (hipStream_t)stream, G);
-            else hipLaunchKernelGGL((gemm_nt_skinny_glu_kernel<2, 1>), grid, dim3(256), 0, (hipStream_t)stream, G);
-        } else {
-            if (gelu_tanh) hipLaunchKernelGGL((gemm_nt_skinny_glu_kernel<8, 2>), grid, dim3(256), 0, (hipStream_t)stream, G);
-            else hipLaunchKernelGGL((gemm_nt_skinny_glu_kernel<8, 1>), grid, dim3(256), 0, (hipStream_t)stream, G);
-        }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nt_skinny_glu_kernel: ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-        return ECGB_OK;
+        const GemmKern kern = M <= 2 ? (gelu_tanh ? (GemmKern)gemm_nt_skinny_glu_kernel<2, 2> : (GemmKern)gemm_nt_skinny_glu_kernel<2, 1>)
+                                     : (gelu_tanh ? (GemmKern)gemm_nt_skinny_glu_kernel<8, 2> : (GemmKern)gemm_nt_skinny_glu_kernel<8, 1>);
+        return ecgb::launch_kernel(kern, dim3((unsigned)((inter + 3) / 4)), dim3(256), 0, stream, "gemm_nt_skinny_glu_kernel", G);
     }
     // whole tiles, no second operand pair: the four-wave kernel with the same epilogue (the same bits).  Measured at [32768, 2048] -> 2 x 8192: 1.853 against 1.863 ms, h only
     // 1.669 against 1.703 -- the activation is vector work that a wave alone on its SIMD cannot hide (under the profiler its MFMA pipes are 0.57 busy, the plain kernel's
     // 0.65); with a LoRA pair behind it 1.952 against 1.935 in round 3 -- and 1.75 against 1.94 with round 4's K-tile schedule, so that form goes there too now.
-    if (g_gemm_w4 && g_gemm_tile == 0 && (K2 <= 0 || ecgb::gemm_w4_span_ok(0, lda2, ldb2, K2, inter)) && (ldh & 7) == 0 && ((uintptr_t)h_dev & 15) == 0 && (!c_dev || ((ldc & 7) == 0 && ((uintptr_t)c_dev & 15) == 0)) &&
-        ecgb::gemm_w4_span_ok(0, lda, ldb, K, inter) && ecgb::gemm_w4_applies(a_dev, lda, b_dev, ldb, h_dev, ldh, M, 2 * inter, K))
-        return ecgb::gemm_w4_launch(a_dev, lda, b_dev, ldb, c_dev, ldc, M, 2 * inter, K, alpha, stream, gelu_tanh ? 2 : 1, h_dev, ldh, a2_dev, lda2, b2_dev, ldb2, K2, nullptr, nullptr, 0, 0);
-    GemmArgs G{};
-    G.group_m = g_gemm_group_m;
-    G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = c_dev;
-    G.M = M; G.N = 2 * inter; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = ldc;
-    G.batch_a = G.batch_b = G.batch_c = 0;
-    G.accumulate_f32 = 0; G.alpha = alpha;
-    G.A2 = (const unsigned short *)a2_dev; G.B2 = (const unsigned short *)b2_dev; G.lda2 = lda2; G.ldb2 = ldb2; G.K2 = K2 > 0 ? K2 : 0;
-    G.inner = 0; G.outer_a = G.inner_a = G.outer_b = G.inner_b = G.outer_c = G.inner_c = 0; G.div_a = G.div_b = 1;
-    G.H = (unsigned short *)h_dev; G.ldh = ldh; G.glu_I = inter;
+    if ((K2 <= 0 || ecgb::gemm_w4_span_ok(0, lda2, ldb2, K2, inter)) && (ldh & 7) == 0 && ((uintptr_t)h_dev & 15) == 0 && (!c_dev || ((ldc & 7) == 0 && ((uintptr_t)c_dev & 15) == 0)) &&
+        w4_takes(ecgb::W4_NT, a_dev, lda, b_dev, ldb, h_dev, ldh, M, 2 * inter, K, inter)) {
+        ecgb::W4Launch L{a_dev, lda, b_dev, ldb, c_dev, ldc, M, 2 * inter, K, alpha, stream};
+        L.epilogue = gelu_tanh ? ecgb::W4_GLU_GELU : ecgb::W4_GLU_SILU;
+        L.h = h_dev; L.ldh = ldh;
+        L.a2 = a2_dev; L.lda2 = lda2; L.b2 = b2_dev; L.ldb2 = ldb2; L.K2 = K2;
+        return ecgb::gemm_w4_launch(L);
+    }
     G.tiles_m = (M + 255) / 256; G.tiles_n = (2 * inter) / 256;
-    constexpr int lds = 2 * (256 + 256) * BK * 2;
-    using Kern = void (*)(GemmArgs);
-    Kern kern = gelu_tanh ? (G.K2 ? (Kern)gemm_nt_kernel_m16p<256, 256, 2, 4, true, 2> : (Kern)gemm_nt_kernel_m16p<256, 256, 2, 4, false, 2>)
-                          : (G.K2 ? (Kern)gemm_nt_kernel_m16p<256, 256, 2, 4, true, 1> : (Kern)gemm_nt_kernel_m16p<256, 256, 2, 4, false, 1>);
-    unsigned grid = (unsigned)(G.tiles_m * G.tiles_n);
-    if (persist_ok(G, 1, true)) {
-        kern = gelu_tanh ? (G.K2 ? (Kern)gemm_nt_kernel_m16pp<true, 2> : (Kern)gemm_nt_kernel_m16pp<false, 2>)
-                         : (G.K2 ? (Kern)gemm_nt_kernel_m16pp<true, 1> : (Kern)gemm_nt_kernel_m16pp<false, 1>);
-        grid = (unsigned)n_cus();
-    }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(kern, dim3(grid, 1, 1), dim3(512), lds, (hipStream_t)stream, G);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nt_kernel (glu): ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-    return ECGB_OK;
+    const bool persist = persist_ok(G, 1, true);
+    const GemmKern kern = persist ? (gelu_tanh ? (G.K2 ? (GemmKern)gemm_nt_kernel_m16pp<true, 2> : (GemmKern)gemm_nt_kernel_m16pp<false, 2>)
+                                               : (G.K2 ? (GemmKern)gemm_nt_kernel_m16pp<true, 1> : (GemmKern)gemm_nt_kernel_m16pp<false, 1>))
+                                  : (gelu_tanh ? (G.K2 ? (GemmKern)gemm_nt_kernel_m16p<256, 256, 2, 4, true, 2> : (GemmKern)gemm_nt_kernel_m16p<256, 256, 2, 4, false, 2>)
+                                               : (G.K2 ? (GemmKern)gemm_nt_kernel_m16p<256, 256, 2, 4, true, 1> : (GemmKern)gemm_nt_kernel_m16p<256, 256, 2, 4, false, 1>));
+    const unsigned grid = persist ? (unsigned)ecgb::device_cus() : (unsigned)(G.tiles_m * G.tiles_n);
+    return ecgb::launch_kernel(kern, dim3(grid), dim3(512), kLds256, stream, "gemm_nt_kernel (glu)", G);
 }
 
 // C[M, N] = alpha * A[M, K] . B[K, N], B row-major (the input gradient dX = dY . W against the weight as nn.Linear stores it, [out, in]):
@@ -2395,30 +2331,18 @@ extern "C" int ecgb_gemm_nn_bf16(const void *a_dev, long long lda, const void *b
     }
     // long contractions of whole tiles, plain store: the four-wave kernel on the NN layout (the same bits; [32768, 16384] . [16384, 2048]: 1.63 against 1.72 ms).  It is
     // persistent: not while a gradient exchange may hold CUs (g_nn_persist, see above).
-    if (g_gemm_w4 && g_nn_persist && g_gemm_tile == 0 && accumulate_f32 == 0 && (((uintptr_t)c_dev & 15) == 0) && (ldc & 7) == 0 && N % 256 == 0 &&
-        ecgb::gemm_w4_span_ok(1, lda, ldb, K, 0) && ecgb::gemm_w4_applies(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K))
-        return ecgb::gemm_w4_launch(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, 0, 1);
-    GemmArgs G{};
-    G.group_m = g_gemm_group_m;
-    G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = c_dev;
-    G.M = M; G.N = N; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = ldc;
-    G.batch_a = G.batch_b = G.batch_c = 0;
-    G.accumulate_f32 = accumulate_f32; G.alpha = alpha;
-    G.A2 = G.B2 = nullptr; G.lda2 = G.ldb2 = 0; G.K2 = 0;
-    G.inner = 0; G.outer_a = G.inner_a = G.outer_b = G.inner_b = G.outer_c = G.inner_c = 0; G.div_a = G.div_b = 1;
-    G.tiles_m = (M + 255) / 256; G.tiles_n = (N + 255) / 256;
-    constexpr int lds = 2 * (256 + 256) * BK * 2;
-    using Kern = void (*)(GemmArgs);
-    Kern kern = gemm_nn_kernel_m16p<256, 256, 2, 4>;
-    unsigned grid = (unsigned)(G.tiles_m * G.tiles_n);
-    if (g_nn_persist && persist_ok(G, 1, false)) { kern = gemm_nn_kernel_m16pp<0>; grid = (unsigned)n_cus(); }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(kern, dim3(grid, 1, 1), dim3(512), lds, (hipStream_t)stream, G);
-        e = hipGetLastError();
+    if (accumulate_f32 == 0 && (((uintptr_t)c_dev & 15) == 0) && (ldc & 7) == 0 && N % 256 == 0 && w4_takes(ecgb::W4_NN, a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K)) {
+        ecgb::W4Launch L{a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream};
+        L.layout = ecgb::W4_NN;
+        return ecgb::gemm_w4_launch(L);
     }
-    if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nn_kernel: ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-    return ECGB_OK;
+    GemmArgs G = gemm_args(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha);
+    G.accumulate_f32 = accumulate_f32;
+    G.tiles_m = (M + 255) / 256; G.tiles_n = (N + 255) / 256;
+    const bool persist = g_nn_persist && persist_ok(G, 1, false);
+    const GemmKern kern = persist ? (GemmKern)gemm_nn_kernel_m16pp<0> : (GemmKern)gemm_nn_kernel_m16p<256, 256, 2, 4>;
+    const unsigned grid = persist ? (unsigned)ecgb::device_cus() : (unsigned)(G.tiles_m * G.tiles_n);
+    return ecgb::launch_kernel(kern, dim3(grid), dim3(512), kLds256, stream, "gemm_nn_kernel", G);
 }
 
 // ecgb_gemm_nn_bf16 for few output tiles and a long contraction (the loss head's input gradient: 1 280 labelled rows x hidden 2048 over a vocabulary of
@@ -2434,23 +2358,12 @@ extern "C" int ecgb_gemm_nn_splitk_bf16(const void *a_dev, long long lda, const 
         ecgb::set_error("ecgb_gemm_nn_splitk_bf16: K % 64, N % 8, 16-byte aligned operands with strides % 8 required");
         return ECGB_ERR_UNSUPPORTED;
     }
-    GemmArgs G{};
-    G.group_m = g_gemm_group_m;
-    G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = slabs_dev;
-    G.M = M; G.N = N; G.K = K; G.lda = lda; G.ldb = ldb; G.ldc = N;
-    G.batch_a = G.batch_b = G.batch_c = 0;
-    G.accumulate_f32 = 3; G.alpha = alpha; G.split_stride = (long long)M * N;
-    G.A2 = G.B2 = nullptr; G.lda2 = G.ldb2 = 0; G.K2 = 0;
-    G.inner = 0; G.outer_a = G.inner_a = G.outer_b = G.inner_b = G.outer_c = G.inner_c = 0; G.div_a = G.div_b = 1;
+    GemmArgs G = gemm_args(a_dev, lda, b_dev, ldb, slabs_dev, N, M, N, K, alpha);
+    G.accumulate_f32 = 3; G.split_stride = (long long)M * N;
     G.tiles_m = (M + 255) / 256; G.tiles_n = (N + 255) / 256;
-    constexpr int lds = 2 * (256 + 256) * BK * 2;
-    auto kern = gemm_nn_kernel_m16p<256, 256, 2, 4>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)(G.tiles_m * G.tiles_n), (unsigned)n_splits, 1), dim3(512), lds, (hipStream_t)stream, G);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nn_kernel (K-slices): ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
+    const int rc = ecgb::launch_kernel(gemm_nn_kernel_m16p<256, 256, 2, 4>, dim3((unsigned)(G.tiles_m * G.tiles_n), (unsigned)n_splits, 1), dim3(512), kLds256, stream,
+                                       "gemm_nn_kernel (K-slices)", G);
+    if (rc != ECGB_OK) return rc;
     return ecgb_sum_slabs_bf16(slabs_dev, (long long)M * N, n_splits, c_dev, (size_t)M * N, 0, stream);
 }
 
@@ -2467,31 +2380,21 @@ extern "C" int ecgb_gemm_nn_glu_bwd_bf16(const void *dy_dev, long long lddy, con
     }
     // whole tiles and a long enough contraction per workgroup: the four-wave kernel on the NN layout with the same epilogue (the same bits; round 4).  Persistent: not
     // while a gradient exchange may hold CUs (g_nn_persist).
-    if (g_gemm_w4 && g_nn_persist && g_gemm_tile == 0 && ecgb::gemm_w4_span_ok(1, lddy, ldw, K, 0) && ecgb::gemm_w4_applies(dy_dev, lddy, w_dev, ldw, d_gate_up_dev, ldd, M, inter, K))
-        return ecgb::gemm_w4_launch(dy_dev, lddy, w_dev, ldw, d_gate_up_dev, ldd, M, inter, K, 1.0f, stream, gelu_tanh ? 5 : 4, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, 0, 1,
-                                    gate_up_dev, ldgu);
-    GemmArgs G{};
-    G.group_m = g_gemm_group_m;
-    G.A = (const unsigned short *)dy_dev; G.B = (const unsigned short *)w_dev; G.C = d_gate_up_dev;
-    G.M = M; G.N = inter; G.K = K; G.lda = lddy; G.ldb = ldw; G.ldc = ldd;
-    G.batch_a = G.batch_b = G.batch_c = 0;
-    G.accumulate_f32 = 0; G.alpha = 1.0f;
-    G.A2 = G.B2 = nullptr; G.lda2 = G.ldb2 = 0; G.K2 = 0;
-    G.inner = 0; G.outer_a = G.inner_a = G.outer_b = G.inner_b = G.outer_c = G.inner_c = 0; G.div_a = G.div_b = 1;
+    if (w4_takes(ecgb::W4_NN, dy_dev, lddy, w_dev, ldw, d_gate_up_dev, ldd, M, inter, K)) {
+        ecgb::W4Launch L{dy_dev, lddy, w_dev, ldw, d_gate_up_dev, ldd, M, inter, K, 1.0f, stream};
+        L.layout = ecgb::W4_NN;
+        L.epilogue = gelu_tanh ? ecgb::W4_GLU_BWD_GELU : ecgb::W4_GLU_BWD_SILU;
+        L.gu = gate_up_dev; L.ldgu = ldgu;
+        return ecgb::gemm_w4_launch(L);
+    }
+    GemmArgs G = gemm_args(dy_dev, lddy, w_dev, ldw, d_gate_up_dev, ldd, M, inter, K, 1.0f);
     G.tiles_m = M / 256; G.tiles_n = inter / 256;
     G.glu_I = inter; G.GU = (const unsigned short *)gate_up_dev; G.ldgu = ldgu;
-    constexpr int lds = 2 * (256 + 256) * BK * 2;
-    using Kern = void (*)(GemmArgs);
-    Kern kern = gelu_tanh ? (Kern)gemm_nn_kernel_m16p<256, 256, 2, 4, 2> : (Kern)gemm_nn_kernel_m16p<256, 256, 2, 4, 1>;
-    unsigned grid = (unsigned)(G.tiles_m * G.tiles_n);
-    if (g_nn_persist && persist_ok(G, 1, false) && (ldgu & 7) == 0) { kern = gelu_tanh ? (Kern)gemm_nn_kernel_m16pp<2> : (Kern)gemm_nn_kernel_m16pp<1>; grid = (unsigned)n_cus(); }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(kern, dim3(grid, 1, 1), dim3(512), lds, (hipStream_t)stream, G);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nn_kernel (GLU backward): ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-    return ECGB_OK;
+    const bool persist = g_nn_persist && persist_ok(G, 1, false) && (ldgu & 7) == 0;
+    const GemmKern kern = persist ? (gelu_tanh ? (GemmKern)gemm_nn_kernel_m16pp<2> : (GemmKern)gemm_nn_kernel_m16pp<1>)
+                                  : (gelu_tanh ? (GemmKern)gemm_nn_kernel_m16p<256, 256, 2, 4, 2> : (GemmKern)gemm_nn_kernel_m16p<256, 256, 2, 4, 1>);
+    const unsigned grid = persist ? (unsigned)ecgb::device_cus() : (unsigned)(G.tiles_m * G.tiles_n);
+    return ecgb::launch_kernel(kern, dim3(grid), dim3(512), kLds256, stream, "gemm_nn_kernel (GLU backward)", G);
 }
 
 // The same on the down-projection site of a LoRA fine-tune: the adapter's share of the input gradient joins the product before the GLU backward,
@@ -2508,14 +2411,17 @@ extern "C" int ecgb_gemm_nn_glu_bwd_lora_bf16(const void *dy_dev, long long lddy
     }
     if (K % BK || M % 256 || inter % 256 || lddy % 8 || ldw % 8 || ldgu % 8 || ldd % 8 || ((uintptr_t)dy_dev & 15) || ((uintptr_t)w_dev & 15) || ((uintptr_t)gate_up_dev & 15) ||
         ((uintptr_t)d_gate_up_dev & 15) || ((uintptr_t)dt_dev & 15) || ((uintptr_t)at_dev & 15) || (long long)M * inter > 0xFFFFFFFFll ||
-        !(g_gemm_w4 && g_nn_persist && g_gemm_tile == 0 && ecgb::gemm_w4_span_ok(1, lddy, ldw, K, 0) && ecgb::gemm_w4_applies(dy_dev, lddy, w_dev, ldw, d_gate_up_dev, ldd, M, inter, K))) {
+        !w4_takes(ecgb::W4_NN, dy_dev, lddy, w_dev, ldw, d_gate_up_dev, ldd, M, inter, K)) {
         ecgb::set_error("ecgb_gemm_nn_glu_bwd_lora_bf16: whole 256x256 tiles with at least the four-wave kernel's share of K-tiles per CU, 16-byte aligned operands");
         return ECGB_ERR_UNSUPPORTED;
     }
-    const unsigned thr = (unsigned)(p * 65536.0f);                                   // as ecgb_lora_down / ecgb_lora_dx fill them (lora.hip)
-    const float lscale = scale / (1.0f - (float)thr / 65536.0f);
-    return ecgb::gemm_w4_launch(dy_dev, lddy, w_dev, ldw, d_gate_up_dev, ldd, M, inter, K, 1.0f, stream, gelu_tanh ? 7 : 6, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, 0, 1,
-                                gate_up_dev, ldgu, dt_dev, at_dev, lscale, thr, (unsigned)(seed ^ (seed >> 32)));
+    ecgb::W4Launch L{dy_dev, lddy, w_dev, ldw, d_gate_up_dev, ldd, M, inter, K, 1.0f, stream};
+    L.layout = ecgb::W4_NN;
+    L.epilogue = gelu_tanh ? ecgb::W4_GLU_BWD_LORA_GELU : ecgb::W4_GLU_BWD_LORA_SILU;
+    L.gu = gate_up_dev; L.ldgu = ldgu;
+    L.dt = dt_dev; L.at = at_dev;
+    w4_lora_dropout(L, scale, p, seed);
+    return ecgb::gemm_w4_launch(L);
 }
 
 // The input gradient of a frozen projection with ONE LoRA module on it (o): dx = bf16(dY . W) + scale / (1 - p) * mask . (dt A) in one launch -- ecgb_gemm_nn_bf16 followed
@@ -2529,14 +2435,16 @@ extern "C" int ecgb_gemm_nn_lora_bf16(const void *dy_dev, long long lddy, const 
     }
     if (K % BK || M % 256 || in % 256 || lddy % 8 || ldw % 8 || lddx % 8 || ((uintptr_t)dy_dev & 15) || ((uintptr_t)w_dev & 15) || ((uintptr_t)dx_dev & 15) ||
         ((uintptr_t)dt_dev & 15) || ((uintptr_t)at_dev & 15) || (long long)M * in > 0xFFFFFFFFll ||
-        !(g_gemm_w4 && g_nn_persist && g_gemm_tile == 0 && ecgb::gemm_w4_span_ok(1, lddy, ldw, K, 0) && ecgb::gemm_w4_applies(dy_dev, lddy, w_dev, ldw, dx_dev, lddx, M, in, K))) {
+        !w4_takes(ecgb::W4_NN, dy_dev, lddy, w_dev, ldw, dx_dev, lddx, M, in, K)) {
         ecgb::set_error("ecgb_gemm_nn_lora_bf16: whole 256x256 tiles with at least the four-wave kernel's share of K-tiles per CU, 16-byte aligned operands");
         return ECGB_ERR_UNSUPPORTED;
     }
-    const unsigned thr = (unsigned)(p * 65536.0f);
-    const float lscale = scale / (1.0f - (float)thr / 65536.0f);
-    return ecgb::gemm_w4_launch(dy_dev, lddy, w_dev, ldw, dx_dev, lddx, M, in, K, 1.0f, stream, 8, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, 0, 1,
-                                nullptr, 0, dt_dev, at_dev, lscale, thr, (unsigned)(seed ^ (seed >> 32)));
+    ecgb::W4Launch L{dy_dev, lddy, w_dev, ldw, dx_dev, lddx, M, in, K, 1.0f, stream};
+    L.layout = ecgb::W4_NN;
+    L.epilogue = ecgb::W4_LORA;
+    L.dt = dt_dev; L.at = at_dev;
+    w4_lora_dropout(L, scale, p, seed);
+    return ecgb::gemm_w4_launch(L);
 }
 
 #ifdef ECGB_PROFILE

@@ -18,6 +18,7 @@
 
 #include <string>
 
+#include "gemm_host.hpp"
 #include "glu_math.hpp"
 #include "tokenizer.hpp"
 
@@ -653,19 +654,23 @@ int g_w4_group_m = 8;
 int g_w4_min_ktiles = 128;      // K-tiles per workgroup from which the entry points of gemm.hip send a problem here (round 3: 256; with round 4's schedule the qkv / o shapes gain too)
 int g_w4_sched = 1;              // 1: four barriers per K-tile with counted waits (round 4); 0: one rendezvous per K-tile (round 3), kept for A/B
 
-// CUs of the current device, rounded down to a multiple of the 8 XCDs (one persistent workgroup each); looked up per device, cached per device
+// CUs of the current device, rounded down to a multiple of the 8 XCDs (one persistent workgroup each)
 int w4_cus()
 {
-    static int cached[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!cached[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cached[dev] = (n & ~7) > 0 ? (n & ~7) : 8;
-    }
-    return cached[dev];
+    const int n = ecgb::device_cus() & ~7;
+    return n > 0 ? n : 8;
 }
+
+// The kernels that exist, by what they are: layout, epilogue, whether a second operand pair follows the first; kern[s]: the K-tile schedule (g_w4_sched)
+using W4Kern = void (*)(W4Args);
+struct W4Variant { int layout, epilogue; bool cat; W4Kern kern[2]; };
+#define W4_VARIANT(LAY, EPI, CAT) {ecgb::LAY, ecgb::EPI, CAT, {gemm_nt_w4_kernel<ecgb::EPI, CAT, ecgb::LAY, 0>, gemm_nt_w4_kernel<ecgb::EPI, CAT, ecgb::LAY, 1>}}
+const W4Variant kW4Variants[] = {
+    W4_VARIANT(W4_NT, W4_PLAIN, false), W4_VARIANT(W4_NT, W4_GLU_SILU, false), W4_VARIANT(W4_NT, W4_GLU_GELU, false), W4_VARIANT(W4_NT, W4_ROPE, false),
+    W4_VARIANT(W4_NT, W4_PLAIN, true), W4_VARIANT(W4_NT, W4_GLU_SILU, true), W4_VARIANT(W4_NT, W4_GLU_GELU, true), W4_VARIANT(W4_NT, W4_ROPE, true),
+    W4_VARIANT(W4_NN, W4_PLAIN, false), W4_VARIANT(W4_TN, W4_PLAIN, false), W4_VARIANT(W4_NN, W4_GLU_BWD_SILU, false), W4_VARIANT(W4_NN, W4_GLU_BWD_GELU, false),
+    W4_VARIANT(W4_NN, W4_GLU_BWD_LORA_SILU, false), W4_VARIANT(W4_NN, W4_GLU_BWD_LORA_GELU, false), W4_VARIANT(W4_NN, W4_LORA, false)};
+#undef W4_VARIANT
 
 }  // namespace
 
@@ -694,43 +699,33 @@ bool gemm_w4_applies(const void *a_dev, long long lda, const void *b_dev, long l
            (long long)(M / 256) * (N / 256) / g_w4_cus * (K / BK) >= g_w4_min_ktiles;
 }
 
-// epi 0: C [M, N] plain.  epi 1 / 2 (SiLU / tanh-GELU): N = 2 * inter, B = [gate rows; up rows], H [M, inter] = act(gate) * up, C (gate|up) may be null.
-int gemm_w4_launch(const void *a_dev, long long lda, const void *b_dev, long long ldb, void *c_dev, long long ldc, int M, int N, int K, float alpha, void *stream,
-                   int epi, void *h_dev, long long ldh, const void *a2_dev, long long lda2, const void *b2_dev, long long ldb2, int K2,
-                   const float *rope_cos, const float *rope_sin, int rope_cols, int lay, const void *gu_dev, long long ldgu,
-                   const void *ldt_dev = nullptr, const void *lat_dev = nullptr, float lscale = 0.f, unsigned lthr = 0, unsigned lseed = 0)
+// Fills the kernel's arguments from a launch description (gemm_host.hpp) and starts one persistent workgroup per CU.
+int gemm_w4_launch(const W4Launch &L)
 {
     W4Args G;
-    G.LDT = (const unsigned short *)ldt_dev; G.LAT = (const unsigned short *)lat_dev; G.lscale = lscale; G.lthr = lthr; G.lseed = lseed;
-    G.GU = (const unsigned short *)gu_dev; G.ldgu = ldgu;
-    G.rope_cos = rope_cos; G.rope_sin = rope_sin; G.rope_cols = rope_cols;
-    G.A2 = (const unsigned short *)a2_dev; G.B2 = (const unsigned short *)b2_dev; G.lda2 = lda2; G.ldb2 = ldb2; G.K2 = K2 > 0 ? K2 : 0;
-    G.A = (const unsigned short *)a_dev; G.B = (const unsigned short *)b_dev; G.C = (unsigned short *)c_dev;
-    G.lda = lda; G.ldb = ldb; G.ldc = ldc; G.M = M; G.N = N; G.K = K; G.tiles_m = M / 256; G.tiles_n = N / 256; G.alpha = alpha; G.group_m = g_w4_group_m;
-    G.H = (unsigned short *)h_dev; G.ldh = ldh; G.glu_I = epi >= 4 ? N : N / 2;
-    const int which = epi >= 4 ? 6 + epi : lay ? 7 + lay : epi + (G.K2 ? 4 : 0);      // (10, 11: the NN product with the GLU backward behind it; 12, 13: and the LoRA adapter's share; 14: the adapter's share and a plain store)
-#define W4_KERNS(S) {gemm_nt_w4_kernel<0, false, 0, S>, gemm_nt_w4_kernel<1, false, 0, S>, gemm_nt_w4_kernel<2, false, 0, S>, gemm_nt_w4_kernel<3, false, 0, S>, \
-                     gemm_nt_w4_kernel<0, true, 0, S>, gemm_nt_w4_kernel<1, true, 0, S>, gemm_nt_w4_kernel<2, true, 0, S>, gemm_nt_w4_kernel<3, true, 0, S>,     \
-                     gemm_nt_w4_kernel<0, false, 1, S>, gemm_nt_w4_kernel<0, false, 2, S>, gemm_nt_w4_kernel<4, false, 1, S>, gemm_nt_w4_kernel<5, false, 1, S>, \
-                     gemm_nt_w4_kernel<6, false, 1, S>, gemm_nt_w4_kernel<7, false, 1, S>, gemm_nt_w4_kernel<8, false, 1, S>}
-    void (*const kerns[2][15])(W4Args) = {W4_KERNS(0), W4_KERNS(1)};
-#undef W4_KERNS
-    void (*kern)(W4Args) = kerns[g_w4_sched ? 1 : 0][which];
+    G.LDT = (const unsigned short *)L.dt; G.LAT = (const unsigned short *)L.at; G.lscale = L.lscale; G.lthr = L.lthr; G.lseed = L.lseed;
+    G.GU = (const unsigned short *)L.gu; G.ldgu = L.ldgu;
+    G.rope_cos = L.rope_cos; G.rope_sin = L.rope_sin; G.rope_cols = L.rope_cols;
+    G.A2 = (const unsigned short *)L.a2; G.B2 = (const unsigned short *)L.b2; G.lda2 = L.lda2; G.ldb2 = L.ldb2; G.K2 = L.K2 > 0 ? L.K2 : 0;
+    G.A = (const unsigned short *)L.a; G.B = (const unsigned short *)L.b; G.C = (unsigned short *)L.c;
+    G.lda = L.lda; G.ldb = L.ldb; G.ldc = L.ldc;
+    G.M = L.M; G.N = L.N; G.K = L.K;
+    G.tiles_m = L.M / 256; G.tiles_n = L.N / 256;
+    G.alpha = L.alpha;
+    G.group_m = g_w4_group_m;
+    G.H = (unsigned short *)L.h; G.ldh = L.ldh; G.glu_I = L.epilogue >= W4_GLU_BWD_SILU ? L.N : L.N / 2;
+    W4Kern kern = nullptr;
+    for (const W4Variant &v : kW4Variants)
+        if (v.layout == L.layout && v.epilogue == L.epilogue && v.cat == (G.K2 > 0)) kern = v.kern[g_w4_sched ? 1 : 0];
+    if (!kern) { ecgb::set_error("gemm_nt_w4_kernel: no kernel of this layout and epilogue"); return ECGB_ERR_INVALID; }
 #ifdef ECGB_PROFILE
-    if (g_w4_sched >= 16 && which == 0) {                                  // timing-only diagnostics of the plain NT kernel
+    if (g_w4_sched >= 16 && L.layout == W4_NT && L.epilogue == W4_PLAIN && !G.K2) {      // timing-only diagnostics of the plain NT kernel
         const int d = g_w4_sched >> 4;
         kern = d == 1 ? gemm_nt_w4_kernel<0, false, 0, 17> : d == 2 ? gemm_nt_w4_kernel<0, false, 0, 33> : d == 3 ? gemm_nt_w4_kernel<0, false, 0, 49> :
                d == 4 ? gemm_nt_w4_kernel<0, false, 0, 65> : d == 7 ? gemm_nt_w4_kernel<0, false, 0, 113> : kern;
     }
 #endif
-    // (the attribute is per device: set on every launch, as everywhere else in the library -- a cached flag would be wrong on a second GPU)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)w4_cus()), dim3(256), kLdsBytes, (hipStream_t)stream, G);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { ecgb::set_error(std::string("gemm_nt_w4_kernel: ") + hipGetErrorString(e)); return ECGB_ERR_HIP; }
-    return ECGB_OK;
+    return launch_kernel(kern, dim3((unsigned)w4_cus()), dim3(256), kLdsBytes, L.stream, "gemm_nt_w4_kernel", G);
 }
 }  // namespace ecgb
 
@@ -765,18 +760,28 @@ extern "C" int ecgb_set_gemm_w4_group_m(int g)
     return ECGB_OK;
 }
 
+namespace {
+// The four-wave kernel by name, plain store, on any layout: whole tiles within the DMA span, whatever the share of K-tiles per CU
+int w4_by_name(const char *who, int layout, const void *a_dev, long long lda, const void *b_dev, long long ldb, void *c_dev, long long ldc, int M, int N, int K,
+               float alpha, void *stream)
+{
+    if (!a_dev || !b_dev || !c_dev || M <= 0 || N <= 0 || K <= 0) { ecgb::set_error(std::string(who) + ": bad argument"); return ECGB_ERR_INVALID; }
+    if (M % 256 || N % 256 || K % BK || lda % 8 || ldb % 8 || ldc % 8 || (((uintptr_t)a_dev | (uintptr_t)b_dev | (uintptr_t)c_dev) & 15) ||
+        !ecgb::gemm_w4_span_ok(layout, lda, ldb, K, 0)) {
+        ecgb::set_error(std::string(who) + ": M, N multiples of 256, K of 64, operands 16-byte aligned with strides % 8 == 0");
+        return ECGB_ERR_UNSUPPORTED;
+    }
+    ecgb::W4Launch L{a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream};
+    L.layout = layout;
+    return ecgb::gemm_w4_launch(L);
+}
+}  // namespace
+
 // The four-wave kernel by name (tests, A/B): ECGB_ERR_UNSUPPORTED where ecgb_gemm_nt_bf16 would fall back to the 8-wave kernels.
 extern "C" int ecgb_gemm_nt_w4_bf16(const void *a_dev, long long lda, const void *b_dev, long long ldb, void *c_dev, long long ldc,
                                     int M, int N, int K, float alpha, void *stream)
 {
-    if (!a_dev || !b_dev || !c_dev || M <= 0 || N <= 0 || K <= 0) { ecgb::set_error("ecgb_gemm_nt_w4_bf16: bad argument"); return ECGB_ERR_INVALID; }
-    (void)ecgb::gemm_w4_applies(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K);          // (device properties)
-    if (M % 256 || N % 256 || K % BK || lda % 8 || ldb % 8 || ldc % 8 || (((uintptr_t)a_dev | (uintptr_t)b_dev | (uintptr_t)c_dev) & 15) ||
-        !ecgb::gemm_w4_span_ok(0, lda, ldb, K, 0)) {
-        ecgb::set_error("ecgb_gemm_nt_w4_bf16: M, N multiples of 256, K of 64, operands 16-byte aligned with strides % 8 == 0");
-        return ECGB_ERR_UNSUPPORTED;
-    }
-    return ecgb::gemm_w4_launch(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0.f, 0, 0);
+    return w4_by_name("ecgb_gemm_nt_w4_bf16", ecgb::W4_NT, a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream);
 }
 
 // The q|k|v projection with RoPE's forward in the epilogue: C = alpha * (A B^T [+ A2 B2^T]), then every head of 64 columns below rope_cols rotated with row t of the
@@ -790,28 +795,24 @@ extern "C" int ecgb_gemm_nt_bf16_rope(const void *a_dev, long long lda, const vo
         ecgb::set_error("ecgb_gemm_nt_bf16_rope: bad argument");
         return ECGB_ERR_INVALID;
     }
-    (void)ecgb::gemm_w4_applies(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K);          // (device properties)
     if (M % 256 || N % 256 || K % BK || K2 % BK || rope_cols % 64 || rope_cols < 0 || rope_cols > N || lda % 8 || ldb % 8 || ldc % 8 || (K2 > 0 && (lda2 % 8 || ldb2 % 8)) ||
         (((uintptr_t)a_dev | (uintptr_t)b_dev | (uintptr_t)c_dev | (uintptr_t)a2_dev | (uintptr_t)b2_dev | (uintptr_t)rope_cos_dev | (uintptr_t)rope_sin_dev) & 15) ||
         !ecgb::gemm_w4_span_ok(0, lda, ldb, K, 0) || (K2 > 0 && !ecgb::gemm_w4_span_ok(0, lda2, ldb2, K2, 0)) || (long long)(M / 256) * (N / 256) < w4_cus()) {
         ecgb::set_error("ecgb_gemm_nt_bf16_rope: whole 256x256 tiles (one per CU at least), K % 64, 16-byte aligned operands required");
         return ECGB_ERR_UNSUPPORTED;
     }
-    return ecgb::gemm_w4_launch(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream, 3, nullptr, 0, a2_dev, lda2, b2_dev, ldb2, K2 > 0 ? K2 : 0, rope_cos_dev, rope_sin_dev, rope_cols, 0, nullptr, 0);
+    ecgb::W4Launch L{a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream};
+    L.epilogue = ecgb::W4_ROPE;
+    L.a2 = a2_dev; L.lda2 = lda2; L.b2 = b2_dev; L.ldb2 = ldb2; L.K2 = K2;
+    L.rope_cos = rope_cos_dev; L.rope_sin = rope_sin_dev; L.rope_cols = rope_cols;
+    return ecgb::gemm_w4_launch(L);
 }
 
 // C = alpha * A . B with B [K, N] row-major on the four-wave kernel (tests, A/B; ecgb_gemm_nn_bf16 dispatches here for long contractions): whole tiles only.
 extern "C" int ecgb_gemm_nn_w4_bf16(const void *a_dev, long long lda, const void *b_dev, long long ldb, void *c_dev, long long ldc,
                                     int M, int N, int K, float alpha, void *stream)
 {
-    if (!a_dev || !b_dev || !c_dev || M <= 0 || N <= 0 || K <= 0) { ecgb::set_error("ecgb_gemm_nn_w4_bf16: bad argument"); return ECGB_ERR_INVALID; }
-    (void)ecgb::gemm_w4_applies(a_dev, lda, a_dev, lda, c_dev, ldc, M, N, K);          // (device properties)
-    if (M % 256 || N % 256 || K % BK || lda % 8 || ldb % 8 || ldc % 8 || (((uintptr_t)a_dev | (uintptr_t)b_dev | (uintptr_t)c_dev) & 15) ||
-        !ecgb::gemm_w4_span_ok(1, lda, ldb, K, 0)) {
-        ecgb::set_error("ecgb_gemm_nn_w4_bf16: M, N multiples of 256, K of 64, operands 16-byte aligned with strides % 8 == 0");
-        return ECGB_ERR_UNSUPPORTED;
-    }
-    return ecgb::gemm_w4_launch(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, 0, 1, nullptr, 0);
+    return w4_by_name("ecgb_gemm_nn_w4_bf16", ecgb::W4_NN, a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream);
 }
 
 // C[M, N] = alpha * A^T . B with A [K, M] and B [K, N] row-major (ecgb_gemm_tn_bf16's product: C = its [N, K] output, K here = its M) on the four-wave kernel, by name:
@@ -819,12 +820,5 @@ extern "C" int ecgb_gemm_nn_w4_bf16(const void *a_dev, long long lda, const void
 extern "C" int ecgb_gemm_tn_w4_bf16(const void *a_dev, long long lda, const void *b_dev, long long ldb, void *c_dev, long long ldc,
                                     int M, int N, int K, float alpha, void *stream)
 {
-    if (!a_dev || !b_dev || !c_dev || M <= 0 || N <= 0 || K <= 0) { ecgb::set_error("ecgb_gemm_tn_w4_bf16: bad argument"); return ECGB_ERR_INVALID; }
-    (void)ecgb::gemm_w4_applies(a_dev, 8, a_dev, 8, c_dev, ldc, M, N, K);              // (device properties)
-    if (M % 256 || N % 256 || K % BK || lda % 8 || ldb % 8 || ldc % 8 || (((uintptr_t)a_dev | (uintptr_t)b_dev | (uintptr_t)c_dev) & 15) ||
-        !ecgb::gemm_w4_span_ok(2, lda, ldb, K, 0)) {
-        ecgb::set_error("ecgb_gemm_tn_w4_bf16: M, N multiples of 256, K of 64, operands 16-byte aligned with strides % 8 == 0");
-        return ECGB_ERR_UNSUPPORTED;
-    }
-    return ecgb::gemm_w4_launch(a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, 0, 2, nullptr, 0);
+    return w4_by_name("ecgb_gemm_tn_w4_bf16", ecgb::W4_TN, a_dev, lda, b_dev, ldb, c_dev, ldc, M, N, K, alpha, stream);
 }

@@ -395,6 +395,99 @@ def test_four_wave_gemm_refuses_operands_its_32_bit_dma_offsets_cannot_span(lib)
     assert ok(0, 0, 2048, 64) == 0
 
 
+_GEMM_P = "a lda b ldb c ldc M N K alpha"
+# entry point -> (argument names in ABI order, a call that passes every argument check -- never made as it stands --, pointer arguments the entry point wants
+# 16-byte aligned, element strides it wants % 8 == 0, the sizes that must be positive, its contraction length, its own limits as (argument changes, return code))
+_GEMM_ENTRY_POINTS = {
+    "ecgb_gemm_nt_bf16": (
+        _GEMM_P + " accumulate batch batch_a batch_b batch_c stream", dict(M=256, N=256, K=128, lda=128, ldb=128, ldc=256, batch=1),
+        "a b", "lda ldb", "M N K batch", "K", []),
+    "ecgb_gemm_nt_bf16_cat": (
+        "a lda b ldb a2 lda2 b2 ldb2 K2 c ldc M N K alpha accumulate stream", dict(M=256, N=256, K=128, K2=64, lda=128, ldb=128, lda2=64, ldb2=64, ldc=256),
+        "a b a2 b2", "lda ldb lda2 ldb2", "M N K K2", "K", [(dict(K2=96), -3)]),
+    "ecgb_gemm_nt_bf16_lora_decode": (
+        "a lda b ldb a2 lda2 alpha b2 ldb2 K2 t64 c ldc M N K epoch stream", dict(M=1, N=256, K=128, K2=16, lda=128, ldb=128, lda2=128, ldb2=16, ldc=256),
+        "a b a2 b2", "lda ldb lda2 ldb2", "M N K K2", "K",
+        [(dict(M=3), -3), (dict(K2=72), -3), (dict(K2=12), -3), (dict(t64=4), -3),
+         (dict(K=8192, lda=8192, ldb=8192, lda2=8192, N=8200), -3)]),      # x W^T one wave per column, x A^T four: two kernel forms
+    "ecgb_gemm_nt_bf16_heads": (
+        _GEMM_P + " accumulate batch inner outer_a inner_a div_a outer_b inner_b div_b outer_c inner_c stream",
+        dict(M=256, N=256, K=128, lda=128, ldb=128, ldc=256, batch=4, inner=2, div_a=1, div_b=1, outer_a=65536, inner_a=32768, outer_b=65536, inner_b=32768),
+        "a b", "lda ldb outer_a inner_a outer_b inner_b", "M N K batch inner div_a div_b", "K", []),
+    "ecgb_gemm_tn_bf16": (
+        _GEMM_P + " splits stream", dict(M=64, N=256, K=256, lda=256, ldb=256, ldc=256, splits=1),
+        "a b", "lda ldb", "M N K", "M",
+        [(dict(N=260), -3), (dict(K=260), -3), (dict(N=4), -3), (dict(K=4), -3), (dict(ldc=130), -3), (dict(c=4), -3), (dict(c=8, splits=2), -3),
+         (dict(splits=0), -1), (dict(splits=65), -1), (dict(lda=1 << 25), -3), (dict(ldb=1 << 25), -3)]),
+    "ecgb_gemm_nt_glu_bf16": (
+        "a lda b ldb a2 lda2 b2 ldb2 K2 c ldc h ldh M N K alpha gelu_tanh stream",
+        dict(M=256, N=256, K=128, K2=64, lda=128, ldb=128, lda2=64, ldb2=64, ldc=512, ldh=256),
+        "a b a2 b2", "lda ldb lda2 ldb2", "M N K", "K",
+        [(dict(K2=96), -3), (dict(N=192), -3), (dict(ldc=130), -3), (dict(ldh=130), -3),
+         (dict(c=4), -3), (dict(h=4), -3)]),
+    "ecgb_gemm_nn_bf16": (
+        _GEMM_P + " accumulate stream", dict(M=256, N=256, K=128, lda=128, ldb=256, ldc=256),
+        "a b", "lda ldb", "M N K", "K", [(dict(N=260), -3), (dict(N=4), -3), (dict(ldb=1 << 25), -3), (dict(lda=1 << 23), -3)]),
+    "ecgb_gemm_nn_splitk_bf16": (
+        "a lda b ldb c slabs M N K splits alpha stream", dict(M=256, N=256, K=128, lda=128, ldb=256, splits=2),
+        "a b slabs", "lda ldb", "M N K", "K",
+        [(dict(splits=0), -1), (dict(splits=65), -1), (dict(N=260), -3), (dict(N=4), -3), (dict(ldb=1 << 25), -3), (dict(lda=1 << 23), -3)]),
+    "ecgb_gemm_nn_glu_bwd_bf16": (
+        "a lda b ldb gu ldgu c ldc M N K gelu_tanh stream", dict(M=256, N=256, K=128, lda=128, ldb=256, ldgu=512, ldc=512),
+        "a b gu c", "lda ldb ldgu ldc", "M N K", "K",
+        [(dict(M=128), -3), (dict(N=128), -3), (dict(ldb=1 << 25), -3), (dict(lda=1 << 23), -3)]),
+    "ecgb_gemm_nn_glu_bwd_lora_bf16": (
+        "a lda b ldb gu ldgu dt at c ldc M N K gelu_tanh scale p seed stream", dict(M=256, N=256, K=128, lda=128, ldb=256, ldgu=512, ldc=512, scale=2.0, p=0.05, seed=7),
+        "a b gu dt at c", "lda ldb ldgu ldc", "M N K", "K",
+        [(dict(p=1.0), -1), (dict(p=-0.25), -1), (dict(M=128), -3), (dict(N=128), -3)]),
+    "ecgb_gemm_nn_lora_bf16": (
+        "a lda b ldb dt at c ldc M N K scale p seed stream", dict(M=256, N=256, K=128, lda=128, ldb=256, ldc=256, scale=2.0, p=0.05, seed=7),
+        "a b dt at c", "lda ldb ldc", "M N K", "K",
+        [(dict(p=1.0), -1), (dict(p=-0.25), -1), (dict(M=128), -3), (dict(N=128), -3)]),
+    "ecgb_gemm_nt_w4_bf16": (
+        _GEMM_P + " stream", dict(M=256, N=256, K=128, lda=128, ldb=128, ldc=256),
+        "a b c", "lda ldb ldc", "M N K", "K", [(dict(M=128), -3), (dict(N=128), -3), (dict(K=1 << 25, lda=1 << 25, ldb=1 << 25), -3)]),
+    "ecgb_gemm_nn_w4_bf16": (
+        _GEMM_P + " stream", dict(M=256, N=256, K=128, lda=128, ldb=256, ldc=256),
+        "a b c", "lda ldb ldc", "M N K", "K", [(dict(M=128), -3), (dict(N=128), -3), (dict(lda=1 << 26), -3)]),
+    "ecgb_gemm_tn_w4_bf16": (
+        _GEMM_P + " stream", dict(M=256, N=256, K=128, lda=256, ldb=256, ldc=256),
+        "a b c", "lda ldb ldc", "M N K", "K", [(dict(M=128), -3), (dict(N=128), -3), (dict(lda=1 << 25), -3)]),
+    "ecgb_gemm_nt_bf16_rope": (
+        "a lda b ldb a2 lda2 b2 ldb2 K2 c ldc M N K alpha cos sin rope_cols stream",
+        dict(M=256, N=256, K=128, K2=64, lda=128, ldb=128, lda2=64, ldb2=64, ldc=256, rope_cols=128),
+        "a b a2 b2 c cos sin", "lda ldb lda2 ldb2 ldc", "M N K", "K",
+        [(dict(M=128), -3), (dict(N=128), -3), (dict(K2=96), -3),
+         (dict(rope_cols=32), -3), (dict(rope_cols=-64), -3), (dict(rope_cols=320), -3)]),
+}
+
+
+_GEMM_MAY_BE_NULL = {"ecgb_gemm_nt_glu_bf16": ("c",)}      # (inference needs only act(gate) * up)
+
+
+def test_gemm_entry_points_return_codes(lib):
+    """Every GEMM entry point refuses a bad call with the code its argument checks give -- ECGB_ERR_INVALID (-1) for a null operand, a non-positive size or a limit
+    of its own, ECGB_ERR_UNSUPPORTED (-3) for a contraction off the K-step, an operand off 16-byte alignment or a stride off 8 elements -- and names itself in
+    ecgb_last_error().  Each call below is refused before anything touches a device: the operands are addresses inside one host buffer and are never read."""
+    buf = (C.c_uint8 * 4096)()
+    base = (C.addressof(buf) + 63) & ~63
+    scalars = dict(alpha=1.0, scale=1.0, p=0.0, seed=0, accumulate=0, gelu_tanh=0, stream=None, batch_a=0, batch_b=0, batch_c=0, outer_c=0, inner_c=0)
+    for name, (names, good, aligned, strides, sizes, contraction, own) in _GEMM_ENTRY_POINTS.items():
+        names = names.split()
+        pointers = [n for n in names if n not in good and n not in scalars]
+        assert "a" in pointers and "b" in pointers and "c" in pointers, name
+        cases = [({n: None}, -1) for n in pointers if n not in _GEMM_MAY_BE_NULL.get(name, ())] + [({n: v}, -1) for n in sizes.split() for v in (0, -256)]
+        cases += [({contraction: good[contraction] + 32}, -3)] + [({n: 2}, -3) for n in aligned.split()] + [({n: good[n] + 4}, -3) for n in strides.split()]
+        for change, want in cases + own:
+            args = dict(scalars, **good)
+            args.update({n: base + 256 * i for i, n in enumerate(pointers)})
+            # (a pointer case gives the offset from the aligned address, or None)
+            args.update({n: (v if n not in pointers else None if v is None else args[n] + v) for n, v in change.items()})
+            rc = getattr(lib, name)(*[args[n] for n in names])
+            msg = (lib.ecgb_last_error() or b"").decode()
+            assert rc == want and msg.startswith(name + ":"), (name, change, rc, msg)
+
+
 def test_bench_dump_outputs_sample_and_budget(tmp_path):
     """bench.py --dump-outputs: every record's count, a seeded sample of records' ids cut at their counts (-1 past them),
     the same sample on every call, float32 only, and the ids under the budget however long a record is."""
