@@ -228,6 +228,9 @@ __global__ void __launch_bounds__(kFT) features_kernel(FeatArgs A)
         __syncthreads();
         f[7] = total; f[8] = psd[s_int[1]]; f[9] = (double)s_int[1] * fstep;
         f[10] = total > 0.0 ? csum / total : 0.0;
+        // a constant lead has no spectrum: exactly 0, whatever rounding leaves of the detrended segment (scipy keeps that noise: for 0.1 a total near
+        // 8e-34 and a "centroid" of fstep / 3, the Hann window's own)
+        if (vmax == vmin) { f[7] = 0.0; f[8] = 0.0; f[9] = 0.0; f[10] = 0.0; }
         __syncthreads();
     }
 
@@ -265,8 +268,9 @@ __global__ void __launch_bounds__(kFT) features_kernel(FeatArgs A)
         for (int i = t; i < m; i += kFT) keep[i] = 1;
         __syncthreads();
         if (t == 0) {
-            // scipy's _select_by_peak_distance: candidates by descending height, equal heights by descending position (numpy's stable argsort of
-            // <= 16 values, iterated from the end); a kept peak removes its unprocessed neighbours closer than `distance`.
+            // scipy's _select_by_peak_distance: candidates by descending height; a kept peak removes its unprocessed neighbours closer than `distance`.
+            // Equal heights go later position first (a stable sort walked from the end): the project's rule.  scipy walks numpy's default argsort, which is
+            // not stable, so its order among equal heights follows no rule and differs from this one on some leads (morphology.py, deliberate differences).
             for (;;) {
                 int j = -1;
                 for (int u = 0; u < m; ++u)

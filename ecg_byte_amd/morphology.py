@@ -11,6 +11,14 @@ Deliberate differences from the reference:
   * stratified_sampling draws with random.Random(seed), over the clusters in ascending order, and fills the remainder from the unsampled files in
     their input order (the reference draws from an unseeded `random` and a `set`, whose order varies between runs);
   * a file holding a NaN / infinity raises ValueError naming it (the reference fails later, inside PCA).
+  * find_peaks candidates of exactly equal height are taken "later position first" (a stable sort walked from the end).  The reference's order
+    there is whatever numpy's default argsort gives, which follows no rule: restating scipy's selection with a stable sort differed from
+    scipy.signal.find_peaks on 16 of 200 seeded leads with 3-16 equal-height candidates and on 98 of 200 with 17-119 (numpy 2.2.6, AVX-512 sort);
+    with np.argsort's own order it matched 200 of 200.  Ties are common in quantised records: synth_ecg(20, 2500, seed=1) rounded to a step of 0.005
+    has them in 230 of 240 leads, to 0.001 in 106.  Without equal heights the two agree exactly;
+  * a constant lead (max == min) gets exactly 0 for total power, peak power, dominant frequency and spectral centroid.  The reference keeps the
+    rounding noise of scipy's Welch there: for a constant 0.1 a total power near 8e-34 and a "centroid" of 0.08138... = fstep / 3, the Hann window's
+    own.
 """
 from __future__ import annotations
 

@@ -38,13 +38,13 @@ def _edge_leads(L):
     return np.stack(leads)
 
 
-def _check_features(x):
+def _check_features(x, peaks="scipy"):
     got, flags = M.features(torch.from_numpy(x).cuda())
     got = got.cpu().numpy().reshape(len(x), 12, 24)
     assert not flags.any()
     for r in range(len(x)):
         for l in range(12):
-            want, _ = R.lead_features(x[r, l])
+            want, _ = R.lead_features(x[r, l], peaks=peaks)
             g = got[r, l]
             for q in R.EXACT:
                 assert g[q] == want[q], (r, l, q, g[q], want[q])
