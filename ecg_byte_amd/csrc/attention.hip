@@ -1,4 +1,5 @@
-// attention.hip -- fused causal grouped-query attention for MI355X (gfx950): forward, dQ, dK/dV.
+// attention.hip -- fused causal grouped-query attention for MI355X (gfx950): forward, dQ, dK/dV of a training step (a decode step's attention against the KV cache:
+// attention_decode.hip).
 //
 // Reference: LlamaSdpaAttention.forward + the 4-D causal/left-padding mask
 // (transformers/src/transformers/models/llama/modeling_llama.py:526-614, 981-1100): key j is visible
@@ -1416,511 +1417,6 @@ __global__ __launch_bounds__(256) void attn_dkv_reduce_kernel(AttnArgs A)
     }
 }
 
-// =====================================================================================================
-// decode step: one query per (batch, head) against the KV cache.  grid (Hq, B), 16 waves per workgroup; head_dim 64 / 128 / 256.
-// q [B, Hq*D]; k/v cache rows [B, cap] with row stride ld (elements), kv head g at + g*D; len = keys in the cache
-// (incl. the new one); key j visible iff mask[b, j] != 0.  Reads the cache once, every row as one coalesced D*2-byte piece:
-//   scores  a wave takes keys w, w+16, ...: its lanes read a key row together (D/64 elements each), multiply with the
-//           query (registers) and add up across the wave; eight keys in flight per wave;
-//   softmax max and sum over the workgroup, probabilities in LDS (fp32);
-//   P.V     thread t owns one 16-byte piece of the value rows of its key slice (interleaved keys); the slices' partial
-//           sums meet in LDS in a fixed order.  P is cast to bf16 before P.V, as SDPA does.
-constexpr int kDecodeThreads = 1024;
-template <int D>
-__global__ __launch_bounds__(kDecodeThreads) void attn_decode_kernel(const unsigned short *q, const unsigned short *kc, const unsigned short *vc,
-                                                                     long long ld, long long cap, const float *mask, long long mask_ld,
-                                                                     unsigned short *o, int len_arg, const int *len_dev, int Hq, int Hkv, float scale)
-{
-    constexpr int NW = kDecodeThreads / 64, EPL = D / 64;   // waves, elements per lane of a key row
-    constexpr int KU = 16, VU = 8;                      // key rows a wave / value rows a thread keeps in flight (memory latency, not bandwidth, is the cost)
-    extern __shared__ float s_p[];                      // [len] scores / probabilities, later [kDecodeThreads * 8] partial outputs; [2 * NW] reductions
-    const int len = len_dev ? *len_dev : len_arg;       // device-resident when the step is replayed from a captured graph
-    const int rows_lds = len_dev ? (((int)cap + 3) & ~3) : ((len + 3) & ~3);
-    float *s_red = s_p + max(rows_lds, kDecodeThreads * 8);   // behind the scores / the P.V partial sums, whichever is longer
-    const int hq = blockIdx.x, b = blockIdx.y, g = hq / (Hq / Hkv), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned short *qp = q + ((long long)b * Hq + hq) * D;
-    float qf[EPL];
-#pragma unroll
-    for (int t = 0; t < EPL; ++t) qf[t] = bf2f(qp[lane * EPL + t]);
-    const unsigned short *K = kc + (long long)b * cap * ld + (long long)g * D;
-    const unsigned short *V = vc + (long long)b * cap * ld + (long long)g * D;
-    const float *mrow = mask + (long long)b * mask_ld;
-
-    // ---- scores
-    float m = -INFINITY;
-    for (int j0 = wave; j0 < len; j0 += KU * NW) {
-        float part[KU], mk[KU];
-#pragma unroll
-        for (int u = 0; u < KU; ++u) mk[u] = mrow[min(j0 + u * NW, len - 1)];   // in flight together with the key rows
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const int j = j0 + u * NW;
-            part[u] = 0.f;
-            if (j < len) {
-                const unsigned short *kr = K + (long long)j * ld + lane * EPL;
-                if constexpr (EPL == 4) {
-                    const uint2 kv = *reinterpret_cast<const uint2 *>(kr);
-                    part[u] = qf[0] * __uint_as_float(kv.x << 16) + qf[1] * __uint_as_float(kv.x & 0xFFFF0000u) +
-                              qf[2] * __uint_as_float(kv.y << 16) + qf[3] * __uint_as_float(kv.y & 0xFFFF0000u);
-                } else if constexpr (EPL == 2) {
-                    const unsigned kv = *reinterpret_cast<const unsigned *>(kr);
-                    part[u] = qf[0] * __uint_as_float(kv << 16) + qf[1] * __uint_as_float(kv & 0xFFFF0000u);
-                } else {
-                    part[u] = qf[0] * bf2f(kr[0]);
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-            for (int u = 0; u < KU; ++u) part[u] += __shfl_xor(part[u], d, 64);
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const int j = j0 + u * NW;
-            if (j < len) {
-                const float sdot = (mk[u] != 0.f) ? part[u] * scale : -INFINITY;
-                if (lane == 0) s_p[j] = sdot;
-                m = fmaxf(m, sdot);
-            }
-        }
-    }
-    if (lane == 0) s_red[wave] = m;
-    __syncthreads();
-    m = s_red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) m = fmaxf(m, s_red[w]);
-
-    // ---- softmax
-    float l = 0.f;
-    for (int j = tid; j < len; j += kDecodeThreads) {
-        const float e = (m == -INFINITY) ? 0.f : __expf(s_p[j] - m);
-        s_p[j] = e;
-        l += e;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) l += __shfl_xor(l, d, 64);
-    if (lane == 0) s_red[NW + wave] = l;
-    __syncthreads();
-    l = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) l += s_red[NW + w];
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-
-    // ---- P.V: thread t owns 8 consecutive output dimensions (one 16-byte piece of a value row) and the keys of slice
-    // t / (D / 8), interleaved; all of a thread's rows of a batch are in flight together
-    constexpr int TPR = D / 8, NS = kDecodeThreads / TPR;      // threads per value row, key slices
-    const int piece = tid % TPR, slice = tid / TPR;
-    float acc[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) acc[t] = 0.f;
-    for (int j0 = slice; j0 < len; j0 += VU * NS) {
-        bf16x8 vv[VU];
-#pragma unroll
-        for (int u = 0; u < VU; ++u) {
-            const int j = min(j0 + u * NS, len - 1);                    // past the end: a repeated row with probability 0
-            vv[u] = *reinterpret_cast<const bf16x8 *>(V + (long long)j * ld + piece * 8);
-        }
-#pragma unroll
-        for (int u = 0; u < VU; ++u) {
-            const int j = j0 + u * NS;
-            const float pj = (j < len) ? bf2f((unsigned short)(pack_bf16(s_p[j] * inv, 0.f) & 0xFFFFu)) : 0.f;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) acc[t] += pj * bf2f((unsigned short)vv[u][t]);
-        }
-    }
-    __syncthreads();                                            // s_p is dead: the slices' partial sums go there
-    float *s_part = s_p;                                        // [NS][D] floats (the launch sizes the buffer for it)
-#pragma unroll
-    for (int t = 0; t < 8; ++t) s_part[slice * D + piece * 8 + t] = acc[t];
-    __syncthreads();
-    if (tid < D) {
-        float sum = 0.f;
-#pragma unroll 8
-        for (int sl = 0; sl < NS; ++sl) sum += s_part[sl * D + tid];
-        o[((long long)b * Hq + hq) * D + tid] = (unsigned short)(pack_bf16(sum, 0.f) & 0xFFFFu);
-    }
-}
-
-// ---- the same decode step with the keys of a head split over several workgroups (long caches, few heads: one CU
-// sustains only ~64 GB/s at the memory latency, the chip has 256).  Three small kernels:
-//   scores   grid (splits, Hq, B): the scores of the split's keys to scratch (fp32) + the split's max and sum of exponentials;
-//   values   grid (splits, Hq, B): global max / sum from the splits' statistics, p_j = bf16(exp(s_j - max) / sum) exactly as
-//            attn_decode_kernel forms it, partial P.V of the split's keys to scratch (fp32);
-//   combine  grid (Hq, B): the partial outputs added in split order, cast to bf16.
-// scratch (floats): scores [B, Hq, cap] | stats [B, Hq, splits, 2] | partial outputs [B, Hq, splits, D].
-constexpr int kSplitThreads = 256;
-constexpr int kSplitMaxChunk = 2048;                     // keys per split the scores kernel can hold (the launcher raises n_splits to fit)
-template <int D>
-__global__ __launch_bounds__(kSplitThreads) void attn_decode_scores_kernel(const unsigned short *q, const unsigned short *kc, long long ld, long long cap,
-                                                                           const float *mask, long long mask_ld, float *scores, float *stats,
-                                                                           int len_arg, int chunk_arg, const int *len_dev, int Hq, int Hkv, float scale)
-{
-    constexpr int NW = kSplitThreads / 64, EPL = D / 64, KU = 16;
-    __shared__ float s_red[2 * NW];
-    __shared__ float s_sc[kSplitMaxChunk];                // the split's scores once more: the sum of exponentials reads them here
-    const int sp = blockIdx.x, hq = blockIdx.y, b = blockIdx.z, g = hq / (Hq / Hkv), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // device-resident length (a replayed graph): the same split of the keys the host computes from a length it knows
-    const int len = len_dev ? *len_dev : len_arg, chunk = len_dev ? (len + (int)gridDim.x - 1) / (int)gridDim.x : chunk_arg;
-    const int k0 = sp * chunk, k1 = min(len, k0 + chunk);
-    const unsigned short *qp = q + ((long long)b * Hq + hq) * D;
-    float qf[EPL];
-#pragma unroll
-    for (int t = 0; t < EPL; ++t) qf[t] = bf2f(qp[lane * EPL + t]);
-    const unsigned short *K = kc + (long long)b * cap * ld + (long long)g * D;
-    const float *mrow = mask + (long long)b * mask_ld;
-    float *srow = scores + ((long long)b * Hq + hq) * cap;
-    float m = -INFINITY;
-    for (int j0 = k0 + wave; j0 < k1; j0 += KU * NW) {
-        float part[KU], mk[KU];
-#pragma unroll
-        for (int u = 0; u < KU; ++u) mk[u] = mrow[min(j0 + u * NW, k1 - 1)];
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const int j = j0 + u * NW;
-            part[u] = 0.f;
-            if (j < k1) {
-                const unsigned short *kr = K + (long long)j * ld + lane * EPL;
-                if constexpr (EPL == 4) {
-                    const uint2 kv = *reinterpret_cast<const uint2 *>(kr);
-                    part[u] = qf[0] * __uint_as_float(kv.x << 16) + qf[1] * __uint_as_float(kv.x & 0xFFFF0000u) +
-                              qf[2] * __uint_as_float(kv.y << 16) + qf[3] * __uint_as_float(kv.y & 0xFFFF0000u);
-                } else if constexpr (EPL == 2) {
-                    const unsigned kv = *reinterpret_cast<const unsigned *>(kr);
-                    part[u] = qf[0] * __uint_as_float(kv << 16) + qf[1] * __uint_as_float(kv & 0xFFFF0000u);
-                } else {
-                    part[u] = qf[0] * bf2f(kr[0]);
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-            for (int u = 0; u < KU; ++u) part[u] += __shfl_xor(part[u], d, 64);
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const int j = j0 + u * NW;
-            if (j < k1) {
-                const float sdot = (mk[u] != 0.f) ? part[u] * scale : -INFINITY;
-                if (lane == 0) { srow[j] = sdot; s_sc[j - k0] = sdot; }
-                m = fmaxf(m, sdot);
-            }
-        }
-    }
-    if (lane == 0) s_red[wave] = m;
-    __syncthreads();
-    m = s_red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) m = fmaxf(m, s_red[w]);
-    float l = 0.f;
-    for (int j = k0 + tid; j < k1; j += kSplitThreads) l += (m == -INFINITY) ? 0.f : __expf(s_sc[j - k0] - m);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) l += __shfl_xor(l, d, 64);
-    if (lane == 0) s_red[NW + wave] = l;
-    __syncthreads();
-    if (tid == 0) {
-        l = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) l += s_red[NW + w];
-        float *st = stats + (((long long)b * Hq + hq) * gridDim.x + sp) * 2;
-        st[0] = m;
-        st[1] = l;
-    }
-}
-
-template <int D>
-__global__ __launch_bounds__(kSplitThreads) void attn_decode_values_kernel(const unsigned short *vc, long long ld, long long cap, const float *scores,
-                                                                           const float *stats, float *partial, int len_arg, int chunk_arg, const int *len_dev,
-                                                                           int Hq, int Hkv)
-{
-    constexpr int TPR = D / 8, NS = kSplitThreads / TPR, VU = 8;
-    __shared__ float s_part[NS * D];
-    const int sp = blockIdx.x, hq = blockIdx.y, b = blockIdx.z, g = hq / (Hq / Hkv), tid = threadIdx.x;
-    const int n_splits = gridDim.x;
-    const int len = len_dev ? *len_dev : len_arg, chunk = len_dev ? (len + n_splits - 1) / n_splits : chunk_arg;
-    const int k0 = sp * chunk, k1 = min(len, k0 + chunk);
-    const float *st = stats + ((long long)b * Hq + hq) * n_splits * 2;
-    float m = -INFINITY;
-    for (int t = 0; t < n_splits; ++t) m = fmaxf(m, st[2 * t]);
-    float l = 0.f;
-    for (int t = 0; t < n_splits; ++t) l += (st[2 * t] == -INFINITY) ? 0.f : st[2 * t + 1] * __expf(st[2 * t] - m);
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-    const unsigned short *V = vc + (long long)b * cap * ld + (long long)g * D;
-    const float *srow = scores + ((long long)b * Hq + hq) * cap;
-    const int piece = tid % TPR, slice = tid / TPR;
-    float acc[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) acc[t] = 0.f;
-    for (int j0 = k0 + slice; j0 < k1; j0 += VU * NS) {
-        bf16x8 vv[VU];
-        float sc[VU];
-#pragma unroll
-        for (int u = 0; u < VU; ++u) {
-            const int j = min(j0 + u * NS, k1 - 1);
-            vv[u] = *reinterpret_cast<const bf16x8 *>(V + (long long)j * ld + piece * 8);
-            sc[u] = srow[j];
-        }
-#pragma unroll
-        for (int u = 0; u < VU; ++u) {
-            const int j = j0 + u * NS;
-            const float e = (m == -INFINITY) ? 0.f : __expf(sc[u] - m);
-            const float pj = (j < k1) ? bf2f((unsigned short)(pack_bf16(e * inv, 0.f) & 0xFFFFu)) : 0.f;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) acc[t] += pj * bf2f((unsigned short)vv[u][t]);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) s_part[slice * D + piece * 8 + t] = acc[t];
-    __syncthreads();
-    if (tid < D) {
-        float sum = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) sum += s_part[sl * D + tid];
-        partial[(((long long)b * Hq + hq) * n_splits + sp) * D + tid] = sum;
-    }
-}
-
-template <int D>
-__global__ __launch_bounds__(D) void attn_decode_combine_kernel(const float *partial, unsigned short *o, int n_splits, int Hq)
-{
-    const int hq = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const float *p = partial + ((long long)b * Hq + hq) * n_splits * D + tid;
-    float sum = 0.f;
-    for (int t = 0; t < n_splits; ++t) sum += p[(long long)t * D];
-    o[((long long)b * Hq + hq) * D + tid] = (unsigned short)(pack_bf16(sum, 0.f) & 0xFFFFu);
-}
-
-// ---- round 6: the four launches of a decode step's attention (rope_append, scores, values, combine: 4.8 + 11.2 + 5.3 + 4.8 us a layer in the replayed graph at the
-// C5 shape, every one of them on the ~5 us floor of a dependent launch) as ONE.  grid (splits, Hq, B) as the split kernels; the workgroups of a (sequence, head) meet
-// twice through counters in device memory:
-//   0  RoPE of the head's q and of the KV head's new key in LDS (rope_append_kernel's arithmetic; the workgroup of split 0 of the group's first head writes the rotated
-//      key and the value to cache row len - 1 -- nobody reads that row in this launch: the split that owns key len - 1 takes it from LDS / from qkv)
-//   1  the split's scores into LDS, its maximum and sum of exponentials to `stats` (attn_decode_scores_kernel's sums);  wait until every split's pair is there (a pair holds kDecodeOneEmpty until stored)
-//   2  softmax over the splits' statistics, P.V of the split's keys (attn_decode_values_kernel's sums) to `partial`;  counter B: the last to arrive adds the
-//      partial outputs in split order (attn_decode_combine_kernel), puts the empty marks back and clears the counter for the next launch (a replayed graph never does itself).
-// The same arithmetic in the same order: the same bits as the four launches (tests/test_gpu_decode_fused.py).  The wait in step 1 needs every workgroup of the
-// launch resident at once: the host only takes this form for splits * Hq * B <= two workgroups a CU.
-// "not stored yet" in the splits' statistics: a NaN with a payload no arithmetic produces (a sum or maximum that IS NaN -- garbage in -- is the canonical one and ends the wait like any value)
-constexpr unsigned kDecodeOneEmpty = 0x7FC0DEADu;
-struct DecodeOneArgs {
-    const unsigned short *qkv;    // [B, (Hq + 2 Hkv) D]: the step's projection, not written (q and the new key are rotated into LDS)
-    long long ld_qkv;
-    const float *cs, *sn;         // RoPE tables of the step's positions [B, D / 2]
-    unsigned short *cache;        // [B, cap, ld]: keys | values
-    long long cap, ld;
-    const float *mask;
-    long long mask_ld;
-    float *stats, *partial;       // [B, Hq, splits, 2] (kDecodeOneEmpty between launches), [B, Hq, splits, D]
-    unsigned *cnt;                // [B, Hq, 2], zero between launches (word 1: the tickets of the second meeting)
-    unsigned short *o;            // [B, Hq D]
-    const int *len_dev;
-    int len_arg, Hq, Hkv;
-    float scale;
-};
-
-template <int D>
-__global__ __launch_bounds__(kSplitThreads) void attn_decode_one_kernel(DecodeOneArgs A)
-{
-    constexpr int NW = kSplitThreads / 64, EPL = D / 64, KU = 16, half = D / 2;
-    constexpr int TPR = D / 8, NS = kSplitThreads / TPR, VU = 8;
-    __shared__ __attribute__((aligned(16))) unsigned short s_q[D], s_kn[D];
-    __shared__ float s_red[2 * NW];
-    __shared__ float s_sc[kSplitMaxChunk];
-    __shared__ float s_part[NS * D];
-    __shared__ float s_st[2 * 64];                         // the splits' (maximum, sum) pairs (splits <= 64)
-    __shared__ unsigned s_last;
-    const int sp = blockIdx.x, hq = blockIdx.y, b = blockIdx.z, G = A.Hq / A.Hkv, g = hq / G, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n_splits = gridDim.x;
-    const int len = A.len_dev ? *A.len_dev : A.len_arg, chunk = (len + n_splits - 1) / n_splits;
-    const int k0 = sp * chunk, k1 = min(len, k0 + chunk);
-    const unsigned short *row = A.qkv + (long long)b * A.ld_qkv;
-    auto bf = [](float x) { return (unsigned short)(pack_bf16(x, 0.f) & 0xFFFFu); };
-    // Memory between the workgroups of a (sequence, head): everything they exchange (statistics, partial outputs, counters) is written and read with agent-scope
-    // RELAXED atomics -- stores that go through to the level the XCDs share, loads that do not stop at this XCD's L2 -- ordered by hand: a wave's stores are
-    // complete (s_waitcnt vmcnt(0)) before its workgroup's counter moves.  Release / acquire orderings on the counters cost a write-back of the whole L2 per
-    // arrival and an invalidate per poll: the launch took 24 us that way, as long as the four it replaces.
-    auto ld_f = [](const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto st_f = [](float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    const unsigned short *K = A.cache + (long long)b * A.cap * A.ld + (long long)g * D;
-    const unsigned short *V = A.cache + (long long)b * A.cap * A.ld + (long long)A.Hkv * D + (long long)g * D;
-    const unsigned short *vnew = row + (long long)(A.Hq + A.Hkv + g) * D;
-    const float *mrow = A.mask + (long long)b * A.mask_ld;
-    const int piece = tid % TPR, slice = tid / TPR;
-    // ---- the first batch of keys and values is asked for before anything else (a split of the C5 step is one batch: 61 keys): the loads fly under the RoPE and
-    // the values' under the scores and the first meeting
-    using kraw_t = uint2;                                                      // EPL elements of a key row as raw bits (EPL 4: 8 bytes, 2: 4, 1: 2)
-    kraw_t kraw[KU];
-    float mk0[KU];
-    auto load_k = [&](int j0, kraw_t (&kr)[KU], float (&mk)[KU]) {
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const int j = min(j0 + u * NW, k1 - 1);
-            mk[u] = mrow[j];
-            const unsigned short *p = K + (long long)j * A.ld + lane * EPL;
-            if constexpr (EPL == 4) kr[u] = *reinterpret_cast<const uint2 *>(p);
-            else if constexpr (EPL == 2) { kr[u].x = *reinterpret_cast<const unsigned *>(p); kr[u].y = 0u; }
-            else { kr[u].x = p[0]; kr[u].y = 0u; }
-        }
-    };
-    bf16x8 vraw[VU];
-    auto load_v = [&](int j0, bf16x8 (&vv)[VU]) {
-#pragma unroll
-        for (int u = 0; u < VU; ++u) {
-            const int j = min(j0 + u * NS, k1 - 1);
-            vv[u] = *reinterpret_cast<const bf16x8 *>((j == len - 1 ? vnew : V + (long long)j * A.ld) + piece * 8);
-        }
-    };
-    if (k0 + wave < k1) load_k(k0 + wave, kraw, mk0);
-    if (k0 + slice < k1) load_v(k0 + slice, vraw);
-    // ---- 0: RoPE -- piece c (eight elements) of a head's first half with piece c of its second half
-    if (tid < 2 * (half / 8)) {
-        const int c = tid % (half / 8), h = tid / (half / 8);                  // h 0: the query head; 1: the new key of its KV head
-        const unsigned short *p = row + (long long)(h == 0 ? hq : A.Hq + g) * D + c * 8;
-        bf16x8 a = *reinterpret_cast<const bf16x8 *>(p), bb = *reinterpret_cast<const bf16x8 *>(p + half);
-        const float *pc = A.cs + (size_t)b * half + c * 8, *ps = A.sn + (size_t)b * half + c * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float cc = bf2f(bf(pc[j])), ss = bf2f(bf(ps[j]));
-            const float x1 = bf2f((unsigned short)a[j]), x2 = bf2f((unsigned short)bb[j]);
-            a[j] = (short)bf(x1 * cc - x2 * ss); bb[j] = (short)bf(x2 * cc + x1 * ss);
-        }
-        unsigned short *dst = h == 0 ? s_q : s_kn;
-        *reinterpret_cast<bf16x8 *>(dst + c * 8) = a;
-        *reinterpret_cast<bf16x8 *>(dst + half + c * 8) = bb;
-        if (h == 1 && sp == 0 && hq == g * G) {                                // the append: rotated key
-            unsigned short *kc = A.cache + ((long long)b * A.cap + (len - 1)) * A.ld + (size_t)g * D + c * 8;
-            *reinterpret_cast<bf16x8 *>(kc) = a;
-            *reinterpret_cast<bf16x8 *>(kc + half) = bb;
-        }
-    }
-    if (sp == 0 && hq == g * G && tid >= 128 && tid < 128 + D / 8)             // the append: the value as it is
-        *reinterpret_cast<bf16x8 *>(A.cache + ((long long)b * A.cap + (len - 1)) * A.ld + (size_t)A.Hkv * D + (size_t)g * D + (tid - 128) * 8) =
-            *reinterpret_cast<const bf16x8 *>(vnew + (tid - 128) * 8);
-    __syncthreads();
-    // ---- 1: scores (attn_decode_scores_kernel)
-    float qf[EPL], kn[EPL];
-#pragma unroll
-    for (int t = 0; t < EPL; ++t) { qf[t] = bf2f(s_q[lane * EPL + t]); kn[t] = bf2f(s_kn[lane * EPL + t]); }
-    float m = -INFINITY;
-    for (int j0 = k0 + wave; j0 < k1; j0 += KU * NW) {
-        if (j0 != k0 + wave) load_k(j0, kraw, mk0);
-        float part[KU];
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const int j = j0 + u * NW;
-            part[u] = 0.f;
-            if (j < k1) {
-                if (j == len - 1) {                                            // the new key: its cache row is being written by another workgroup
-                    part[u] = qf[0] * kn[0];
-#pragma unroll
-                    for (int t = 1; t < EPL; ++t) part[u] += qf[t] * kn[t];
-                } else if constexpr (EPL == 4) {
-                    part[u] = qf[0] * __uint_as_float(kraw[u].x << 16) + qf[1] * __uint_as_float(kraw[u].x & 0xFFFF0000u) +
-                              qf[2] * __uint_as_float(kraw[u].y << 16) + qf[3] * __uint_as_float(kraw[u].y & 0xFFFF0000u);
-                } else if constexpr (EPL == 2) {
-                    part[u] = qf[0] * __uint_as_float(kraw[u].x << 16) + qf[1] * __uint_as_float(kraw[u].x & 0xFFFF0000u);
-                } else {
-                    part[u] = qf[0] * bf2f((unsigned short)kraw[u].x);
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-            for (int u = 0; u < KU; ++u) part[u] += __shfl_xor(part[u], d, 64);
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const int j = j0 + u * NW;
-            if (j < k1) {
-                const float sdot = (mk0[u] != 0.f) ? part[u] * A.scale : -INFINITY;
-                if (lane == 0) s_sc[j - k0] = sdot;
-                m = fmaxf(m, sdot);
-            }
-        }
-    }
-    if (lane == 0) s_red[wave] = m;
-    __syncthreads();
-    m = s_red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) m = fmaxf(m, s_red[w]);
-    float l = 0.f;
-    for (int j = k0 + tid; j < k1; j += kSplitThreads) l += (m == -INFINITY) ? 0.f : __expf(s_sc[j - k0] - m);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) l += __shfl_xor(l, d, 64);
-    if (lane == 0) s_red[NW + wave] = l;
-    __syncthreads();
-    float *st = A.stats + ((long long)b * A.Hq + hq) * n_splits * 2;
-    unsigned *cnt = A.cnt + ((long long)b * A.Hq + hq) * 2;
-    if (tid == 0) {
-        l = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) l += s_red[NW + w];
-        st_f(&st[2 * sp], m);
-        st_f(&st[2 * sp + 1], l);
-    }
-    // ---- the first meeting: no counter.  A split's (maximum, sum) pair is kDecodeOneEmpty -- a NaN no sum produces -- until its workgroup has stored it (the scratch starts so and the last workgroup of
-    // the launch puts it back): lane t polls pair t itself -- one round trip from the store to the values, where a counter cost an atomic, a poll and a load
-    if (tid < 2 * n_splits) {
-        const unsigned *sb = reinterpret_cast<const unsigned *>(st) + tid;
-        unsigned v = __hip_atomic_load(sb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (v == kDecodeOneEmpty) { __builtin_amdgcn_s_sleep(1); v = __hip_atomic_load(sb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-        s_st[tid] = __uint_as_float(v);
-    }
-    __syncthreads();
-    // ---- 2: values (attn_decode_values_kernel)
-    m = -INFINITY;
-    for (int t = 0; t < n_splits; ++t) m = fmaxf(m, s_st[2 * t]);
-    l = 0.f;
-    for (int t = 0; t < n_splits; ++t) l += (s_st[2 * t] == -INFINITY) ? 0.f : s_st[2 * t + 1] * __expf(s_st[2 * t] - m);
-    const float inv = l > 0.f ? 1.f / l : 0.f;
-    float acc[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) acc[t] = 0.f;
-    for (int j0 = k0 + slice; j0 < k1; j0 += VU * NS) {
-        if (j0 != k0 + slice) load_v(j0, vraw);
-        float sc[VU];
-#pragma unroll
-        for (int u = 0; u < VU; ++u) sc[u] = s_sc[min(j0 + u * NS, k1 - 1) - k0];
-#pragma unroll
-        for (int u = 0; u < VU; ++u) {
-            const int j = j0 + u * NS;
-            const float e = (m == -INFINITY) ? 0.f : __expf(sc[u] - m);
-            const float pj = (j < k1) ? bf2f(bf(e * inv)) : 0.f;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) acc[t] += pj * bf2f((unsigned short)vraw[u][t]);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) s_part[slice * D + piece * 8 + t] = acc[t];
-    __syncthreads();
-    float *part_out = A.partial + ((long long)b * A.Hq + hq) * n_splits * D;
-    if (tid < D) {
-        float sum = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) sum += s_part[sl * D + tid];
-        st_f(&part_out[(long long)sp * D + tid], sum);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // this wave's part of the partial output has arrived
-    }
-    __syncthreads();
-    if (tid == 0) s_last = __hip_atomic_fetch_add(&cnt[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(n_splits - 1) ? 1u : 0u;
-    __syncthreads();
-    if (!s_last) return;
-    // ---- the last workgroup of the (sequence, head): the splits' partial outputs in split order (attn_decode_combine_kernel)
-    if (tid < D) {
-        float sum = 0.f;
-        for (int t0 = 0; t0 < n_splits; t0 += 16) {                            // sixteen splits' values in flight, added in split order
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = ld_f(&part_out[(long long)min(t0 + u, n_splits - 1) * D + tid]);
-#pragma unroll
-            for (int u = 0; u < 16; ++u) if (t0 + u < n_splits) sum += v[u];
-        }
-        A.o[((long long)b * A.Hq + hq) * D + tid] = bf(sum);
-    }
-    // ready for the next launch: every workgroup of the (sequence, head) has read the statistics (it took its ticket after that)
-    if (tid < 2 * n_splits) st_f(&st[tid], __uint_as_float(kDecodeOneEmpty));
-    if (tid == 0) __hip_atomic_store(&cnt[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // head_dim 64 forward and backward: 2 = the lean kernels (LDS-DMA staging, softmax constants in the MFMA accumulators: the default), 1 = the round-2 LDS-DMA
 // kernels, 0 = the register-staged kernels (tests / A-B).  Bits 8 / 9 / 10 send the forward / dQ / dK-dV kernel alone back to mode 1 (A-B of one kernel).
 int g_attn_dma = 2;
@@ -2165,14 +1661,6 @@ int check_args(const AttnArgs &A, int D, const char *who)
     return ECGB_OK;
 }
 
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return ECGB_OK;
-    ecgb::set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return ECGB_ERR_HIP;
-}
-
 // One kernel launch of the dispatch below: the dynamic-LDS attribute, then the launch; either failure is reported HERE with the kernel's name (a refused
 // attribute used to skip the launch silently and leave it to a later hipGetLastError -- which does not see it: the outputs stayed unwritten, status OK).
 template <typename Kern>
@@ -2365,176 +1853,6 @@ extern "C" int ecgb_attn_bwd_rope(const void *q_dev, long long ldq, const void *
     }
     return attn_bwd_impl(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, do_dev, ldo, lse_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv,
                          batch, seq, n_q_heads, n_kv_heads, head_dim, scale, scratch_dev, scratch_bytes, stream, rope_cos_dev, rope_sin_dev);
-}
-
-namespace {
-int launch_attn_decode(const void *q_dev, const void *k_cache_dev, const void *v_cache_dev, long long ld, long long capacity,
-                       const float *attn_mask_dev, long long mask_ld, void *o_dev, int batch, int kv_len, const int *kv_len_dev,
-                       int n_q_heads, int n_kv_heads, int head_dim, float scale, void *stream)
-{
-    if (head_dim != 64 && head_dim != 128 && head_dim != 256) { ecgb::set_error("ecgb_attn_decode: head_dim must be 64, 128 or 256"); return ECGB_ERR_UNSUPPORTED; }
-    if (batch <= 0 || (!kv_len_dev && (kv_len <= 0 || kv_len > capacity)) || n_q_heads % n_kv_heads || ld % 8) { ecgb::set_error("ecgb_attn_decode: bad shape"); return ECGB_ERR_INVALID; }
-    const long long rows = kv_len_dev ? capacity : (long long)kv_len;
-    const size_t lds = (std::max<size_t>((size_t)((rows + 3) & ~3ll), (size_t)kDecodeThreads * 8) + 2 * (kDecodeThreads / 64)) * 4;
-    if (lds > 64 * 1024) { ecgb::set_error("ecgb_attn_decode: cache longer than ~16000 keys"); return ECGB_ERR_UNSUPPORTED; }
-#define ECGB_DECODE(D_) hipLaunchKernelGGL(attn_decode_kernel<D_>, dim3((unsigned)n_q_heads, (unsigned)batch), dim3(kDecodeThreads), lds, (hipStream_t)stream, \
-        (const unsigned short *)q_dev, (const unsigned short *)k_cache_dev, (const unsigned short *)v_cache_dev, ld, capacity, attn_mask_dev, mask_ld, \
-        (unsigned short *)o_dev, kv_len, kv_len_dev, n_q_heads, n_kv_heads, scale)
-    if (head_dim == 64) ECGB_DECODE(64); else if (head_dim == 128) ECGB_DECODE(128); else ECGB_DECODE(256);
-#undef ECGB_DECODE
-    return launched("attn_decode_kernel");
-}
-
-// cache[b, *len - 1, :] = src[b, col_off : col_off + width]   (the new token's roped K | V, position from device memory)
-__global__ __launch_bounds__(256) void kv_append_kernel(const unsigned short *src, long long src_ld, long long col_off, int width,
-                                                        unsigned short *cache, long long cap, const int *len_dev, int batch)
-{
-    const long long row = *len_dev - 1;
-    const int per_row = width / 8;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < batch * per_row; i += gridDim.x * blockDim.x) {
-        const int b = i / per_row, c = i % per_row;
-        *reinterpret_cast<bf16x8 *>(cache + ((long long)b * cap + row) * width + c * 8) =
-            *reinterpret_cast<const bf16x8 *>(src + (long long)b * src_ld + col_off + c * 8);
-    }
-}
-}  // namespace
-
-extern "C" int ecgb_attn_decode(const void *q_dev, const void *k_cache_dev, const void *v_cache_dev, long long ld, long long capacity,
-                                const float *attn_mask_dev, long long mask_ld, void *o_dev, int batch, int kv_len, int n_q_heads,
-                                int n_kv_heads, int head_dim, float scale, void *stream)
-{
-    return launch_attn_decode(q_dev, k_cache_dev, v_cache_dev, ld, capacity, attn_mask_dev, mask_ld, o_dev, batch, kv_len, nullptr,
-                              n_q_heads, n_kv_heads, head_dim, scale, stream);
-}
-
-extern "C" size_t ecgb_attn_decode_split_scratch_bytes(long long capacity, int batch, int n_q_heads, int head_dim, int n_splits)
-{
-    if (capacity <= 0 || batch <= 0 || n_q_heads <= 0 || n_splits <= 0) return 0;
-    // a split never holds more than kSplitMaxChunk keys: size for the splits the longest cache (capacity keys) can need
-    const long long need_splits = (capacity + kSplitMaxChunk - 1) / kSplitMaxChunk;
-    if (need_splits > n_splits) n_splits = (int)need_splits;
-    return (size_t)batch * n_q_heads * ((size_t)capacity + (size_t)n_splits * (2 + (size_t)head_dim)) * sizeof(float);
-}
-
-namespace {
-int launch_attn_decode_split(const char *who, const void *q_dev, const void *k_cache_dev, const void *v_cache_dev, long long ld, long long capacity,
-                             const float *attn_mask_dev, long long mask_ld, void *o_dev, int batch, int kv_len, const int *kv_len_dev, int n_q_heads,
-                             int n_kv_heads, int head_dim, float scale, int n_splits, void *scratch_dev, size_t scratch_bytes, void *stream)
-{
-    if (head_dim != 64 && head_dim != 128 && head_dim != 256) { ecgb::set_error(std::string(who) + ": head_dim must be 64, 128 or 256"); return ECGB_ERR_UNSUPPORTED; }
-    if (!q_dev || !k_cache_dev || !v_cache_dev || !attn_mask_dev || !o_dev || !scratch_dev || batch <= 0 || (!kv_len_dev && (kv_len <= 0 || kv_len > capacity)) ||
-        capacity <= 0 || n_q_heads <= 0 || n_kv_heads <= 0 || n_q_heads % n_kv_heads || ld % 8 || n_splits <= 0 || n_splits > 1024) {
-        ecgb::set_error(std::string(who) + ": bad argument");
-        return ECGB_ERR_INVALID;
-    }
-    if (scratch_bytes < ecgb_attn_decode_split_scratch_bytes(capacity, batch, n_q_heads, head_dim, n_splits)) {
-        ecgb::set_error(std::string(who) + ": scratch too small (ecgb_attn_decode_split_scratch_bytes)");
-        return ECGB_ERR_INVALID;
-    }
-    // the split count is final BEFORE the scratch is laid out: stats and partial are indexed by gridDim.x.  A length in device memory can grow to the capacity.
-    const long long longest = kv_len_dev ? capacity : (long long)kv_len;
-    if ((longest + n_splits - 1) / n_splits > kSplitMaxChunk) n_splits = (int)((longest + kSplitMaxChunk - 1) / kSplitMaxChunk);
-    float *scores = (float *)scratch_dev;
-    float *stats = scores + (size_t)batch * n_q_heads * (size_t)capacity;
-    float *partial = stats + (size_t)batch * n_q_heads * (size_t)n_splits * 2;
-    const int chunk = kv_len_dev ? 0 : (kv_len + n_splits - 1) / n_splits;
-    const dim3 grid((unsigned)n_splits, (unsigned)n_q_heads, (unsigned)batch), gc((unsigned)n_q_heads, (unsigned)batch);
-#define ECGB_SPLIT(D_) do { \
-        hipLaunchKernelGGL(attn_decode_scores_kernel<D_>, grid, dim3(kSplitThreads), 0, (hipStream_t)stream, (const unsigned short *)q_dev, \
-            (const unsigned short *)k_cache_dev, ld, capacity, attn_mask_dev, mask_ld, scores, stats, kv_len, chunk, kv_len_dev, n_q_heads, n_kv_heads, scale); \
-        hipLaunchKernelGGL(attn_decode_values_kernel<D_>, grid, dim3(kSplitThreads), 0, (hipStream_t)stream, (const unsigned short *)v_cache_dev, \
-            ld, capacity, scores, stats, partial, kv_len, chunk, kv_len_dev, n_q_heads, n_kv_heads); \
-        hipLaunchKernelGGL(attn_decode_combine_kernel<D_>, gc, dim3(D_), 0, (hipStream_t)stream, partial, (unsigned short *)o_dev, n_splits, n_q_heads); \
-    } while (0)
-    if (head_dim == 64) ECGB_SPLIT(64); else if (head_dim == 128) ECGB_SPLIT(128); else ECGB_SPLIT(256);
-#undef ECGB_SPLIT
-    return launched("attn_decode_split kernels");
-}
-}  // namespace
-
-extern "C" int ecgb_attn_decode_split(const void *q_dev, const void *k_cache_dev, const void *v_cache_dev, long long ld, long long capacity,
-                                      const float *attn_mask_dev, long long mask_ld, void *o_dev, int batch, int kv_len, int n_q_heads,
-                                      int n_kv_heads, int head_dim, float scale, int n_splits, void *scratch_dev, size_t scratch_bytes,
-                                      void *stream)
-{
-    return launch_attn_decode_split("ecgb_attn_decode_split", q_dev, k_cache_dev, v_cache_dev, ld, capacity, attn_mask_dev, mask_ld, o_dev, batch, kv_len, nullptr,
-                                    n_q_heads, n_kv_heads, head_dim, scale, n_splits, scratch_dev, scratch_bytes, stream);
-}
-
-extern "C" int ecgb_attn_decode_split_dyn(const void *q_dev, const void *k_cache_dev, const void *v_cache_dev, long long ld, long long capacity,
-                                          const float *attn_mask_dev, long long mask_ld, void *o_dev, int batch, const int *kv_len_dev, int n_q_heads,
-                                          int n_kv_heads, int head_dim, float scale, int n_splits, void *scratch_dev, size_t scratch_bytes,
-                                          void *stream)
-{
-    if (!kv_len_dev) { ecgb::set_error("ecgb_attn_decode_split_dyn: NULL length pointer"); return ECGB_ERR_INVALID; }
-    return launch_attn_decode_split("ecgb_attn_decode_split_dyn", q_dev, k_cache_dev, v_cache_dev, ld, capacity, attn_mask_dev, mask_ld, o_dev, batch, 0, kv_len_dev,
-                                    n_q_heads, n_kv_heads, head_dim, scale, n_splits, scratch_dev, scratch_bytes, stream);
-}
-
-// floats of scratch ecgb_attn_decode_one needs (statistics, partial outputs, counters): before the first call the FIRST batch * n_q_heads * n_splits * 2 floats (the
-// statistics) must hold the bit pattern 0x7FC0DEAD and the LAST batch * n_q_heads * 2 words (the counters) zero; every launch leaves them so
-extern "C" size_t ecgb_attn_decode_one_scratch_floats(int batch, int n_q_heads, int head_dim, int n_splits)
-{
-    if (batch <= 0 || n_q_heads <= 0 || head_dim <= 0 || n_splits <= 0) return 0;
-    return (size_t)batch * n_q_heads * ((size_t)n_splits * (2 + (size_t)head_dim) + 2);
-}
-
-// A decode step's RoPE + cache append + attention in ONE launch, from the step's raw q|k|v projection (q and k NOT rotated in place): the bits of ecgb_rope_append
-// followed by ecgb_attn_decode_split[_dyn] with the same n_splits.  ECGB_ERR_UNSUPPORTED outside head_dim 64 / 128 / 256, n_splits <= 64, at most 2048 keys a split and
-// n_splits * n_q_heads * batch <= two workgroups a CU (they wait for each other inside the launch: all of them must be resident).
-extern "C" int ecgb_attn_decode_one(const void *qkv_dev, long long ld_qkv, const float *cos_dev, const float *sin_dev, void *cache_dev, long long ld, long long capacity,
-                                    const float *attn_mask_dev, long long mask_ld, void *o_dev, int batch, int kv_len, const int *kv_len_dev, int n_q_heads, int n_kv_heads,
-                                    int head_dim, float scale, int n_splits, float *scratch_dev, size_t scratch_floats, void *stream)
-{
-    if (!qkv_dev || !cos_dev || !sin_dev || !cache_dev || !attn_mask_dev || !o_dev || !scratch_dev || batch <= 0 || n_q_heads <= 0 || n_kv_heads <= 0 || n_splits <= 0 ||
-        n_q_heads % n_kv_heads || capacity <= 0 || (!kv_len_dev && (kv_len <= 0 || kv_len > capacity))) {
-        ecgb::set_error("ecgb_attn_decode_one: bad argument");
-        return ECGB_ERR_INVALID;
-    }
-    const long long longest = kv_len_dev ? capacity : (long long)kv_len;
-    int dev = 0, n_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 128;
-    // (two workgroups of 256 threads and 20 KB of LDS a CU are resident whatever else the kernel needs: the launch's workgroups wait for each other)
-    if ((head_dim != 64 && head_dim != 128 && head_dim != 256) || n_splits > 64 || (longest + n_splits - 1) / n_splits > kSplitMaxChunk ||
-        (long long)n_splits * n_q_heads * batch > 2ll * n_cu || ld % 8 || ld_qkv % 8 || ((uintptr_t)qkv_dev & 15) || ((uintptr_t)cache_dev & 15) ||
-        scratch_floats < ecgb_attn_decode_one_scratch_floats(batch, n_q_heads, head_dim, n_splits)) {
-        ecgb::set_error("ecgb_attn_decode_one: head_dim 64 / 128 / 256, at most 64 splits of at most 2048 keys, at most two workgroups a CU, scratch of ecgb_attn_decode_one_scratch_floats()");
-        return ECGB_ERR_UNSUPPORTED;
-    }
-    DecodeOneArgs A;
-    A.qkv = (const unsigned short *)qkv_dev; A.ld_qkv = ld_qkv; A.cs = cos_dev; A.sn = sin_dev; A.cache = (unsigned short *)cache_dev; A.cap = capacity; A.ld = ld;
-    A.mask = attn_mask_dev; A.mask_ld = mask_ld;
-    A.stats = scratch_dev;
-    A.partial = A.stats + (size_t)batch * n_q_heads * n_splits * 2;
-    A.cnt = reinterpret_cast<unsigned *>(A.partial + (size_t)batch * n_q_heads * n_splits * head_dim);
-    A.o = (unsigned short *)o_dev; A.len_dev = kv_len_dev; A.len_arg = kv_len; A.Hq = n_q_heads; A.Hkv = n_kv_heads; A.scale = scale;
-    const dim3 grid((unsigned)n_splits, (unsigned)n_q_heads, (unsigned)batch);
-    if (head_dim == 64) hipLaunchKernelGGL(attn_decode_one_kernel<64>, grid, dim3(kSplitThreads), 0, (hipStream_t)stream, A);
-    else if (head_dim == 128) hipLaunchKernelGGL(attn_decode_one_kernel<128>, grid, dim3(kSplitThreads), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(attn_decode_one_kernel<256>, grid, dim3(kSplitThreads), 0, (hipStream_t)stream, A);
-    return launched("attn_decode_one_kernel");
-}
-
-extern "C" int ecgb_attn_decode_dyn(const void *q_dev, const void *k_cache_dev, const void *v_cache_dev, long long ld, long long capacity,
-                                    const float *attn_mask_dev, long long mask_ld, void *o_dev, int batch, const int *kv_len_dev,
-                                    int n_q_heads, int n_kv_heads, int head_dim, float scale, void *stream)
-{
-    if (!kv_len_dev) { ecgb::set_error("ecgb_attn_decode_dyn: NULL length pointer"); return ECGB_ERR_INVALID; }
-    return launch_attn_decode(q_dev, k_cache_dev, v_cache_dev, ld, capacity, attn_mask_dev, mask_ld, o_dev, batch, 0, kv_len_dev,
-                              n_q_heads, n_kv_heads, head_dim, scale, stream);
-}
-
-extern "C" int ecgb_kv_append(const void *src_dev, long long src_ld, long long col_off, int width, void *cache_dev, long long capacity,
-                              int batch, const int *kv_len_dev, void *stream)
-{
-    if (!src_dev || !cache_dev || !kv_len_dev || width <= 0 || width % 8 || src_ld % 8 || col_off % 8 || batch <= 0) {
-        ecgb::set_error("ecgb_kv_append: bad argument");
-        return ECGB_ERR_INVALID;
-    }
-    const int items = batch * (width / 8);
-    hipLaunchKernelGGL(kv_append_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const unsigned short *)src_dev, src_ld, col_off, width, (unsigned short *)cache_dev, capacity, kv_len_dev, batch);
-    return launched("kv_append_kernel");
 }
 
 #ifdef ECGB_PROFILE

@@ -1,5 +1,6 @@
-// attention_common.inc -- what the attention kernels of attention.hip and attention_d256.hip share: the argument block, the workgroup -> (block, head, batch) map,
-// fragment / store helpers, the key mask in LDS.  Included once per translation unit; everything but ecgb_attn:: has internal linkage.
+// attention_common.inc -- what the attention kernels of attention.hip, attention_d256.hip and attention_decode.hip share: the argument block, the workgroup ->
+// (block, head, batch) map, fragment / store helpers, the key mask in LDS, the launch check.  Included once per translation unit; everything but ecgb_attn:: has
+// internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,6 +62,15 @@ __device__ __forceinline__ float max3(float a, float b, float c)
 __device__ __forceinline__ float bf2f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 
 using ecgb_attn::AttnArgs;
+
+// after a launch: ECGB_OK, or the HIP error under the kernel's name
+inline int launched(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return ECGB_OK;
+    ecgb::set_error(std::string(what) + ": " + hipGetErrorString(e));
+    return ECGB_ERR_HIP;
+}
 
 #ifdef ECGB_PROFILE
 // dev builds only (`make prof`, scripts/dev_prof_attn.py): cycles per phase of the forward loop, summed over waves

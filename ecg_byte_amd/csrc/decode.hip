@@ -17,17 +17,21 @@
 //   4. decode_gemv         o projection; its LoRA down-projection of the attention output in the prologue
 //   5. decode_norm_gemv    (gate|up + GLU, above)
 //   6. decode_lora_t + decode_gemv   down projection (its t over the 16 384-wide GLU output is a kernel of its own: redone per workgroup it would read A 128 times)
-// Arithmetic: every sum is formed in the order the kernels it replaces form it (rmsnorm_lora_fwd_kernel, gemm_nt_skinny_kernel<2, 1 / 4>, gemm_nt_skinny_glu_kernel,
-// rope_append_kernel, attn_decode_scores / values / combine): the same bits, checked op by op in tests/test_gpu_decode_fused.py.
+// Arithmetic: every sum is formed in the order the kernels it replaces form it (rmsnorm_lora_fwd_kernel, gemm_nt_skinny_kernel<2, 1 / 4>, gemm_nt_skinny_glu_kernel);
+// the attention kernels call the routines attention_decode.hip's kernels are made of (decode_attn.inc, rope_math.hpp) and keep only their own loop over the heads of a
+// group: the same bits, checked op by op in tests/test_gpu_decode_fused.py.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
 #include <string>
 
+#include "decode_attn.inc"
 #include "glu_math.hpp"
 #include "tokenizer.hpp"
 
 namespace {
+
+namespace da = ecgb_dattn;
 
 using bf16x8 = __attribute__((ext_vector_type(8))) unsigned short;
 
@@ -401,8 +405,8 @@ struct AttnArgs2 {
     float scale;
 };
 
-// 2: RoPE (q heads of the group and the new key: rope_append_kernel's arithmetic), cache append (split 0 of every (group, sequence)), scores of the split's keys for every
-// head of the group + the split's maximum and sum of exponentials per head (attn_decode_scores_kernel's sums, head by head).  grid (splits, Hkv, B).
+// 2: RoPE (q heads of the group and the new key: ecgb::rope_pair), cache append (split 0 of every (group, sequence)), scores of the split's keys for every head of the
+// group + the split's maximum and sum of exponentials per head (decode_attn.inc's routines, head by head: a key batch is loaded once for the group).  grid (splits, Hkv, B).
 template <int D>
 __global__ __launch_bounds__(kAttnThreads) void decode_attn_scores_kernel(AttnArgs2 A)
 {
@@ -422,13 +426,7 @@ __global__ __launch_bounds__(kAttnThreads) void decode_attn_scores_kernel(AttnAr
         const int c = i % (half / 8), h = i / (half / 8);                  // h < G: query head g G + h; h == G: the new key of KV head g
         const unsigned short *p = row + (long long)(h < G ? g * G + h : A.Hq + g) * D + c * 8;
         bf16x8 a = *reinterpret_cast<const bf16x8 *>(p), bb = *reinterpret_cast<const bf16x8 *>(p + half);
-        const float *pc = A.cs + (size_t)b * half + c * 8, *ps = A.sn + (size_t)b * half + c * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float cc = bf2f(f2bf(pc[j])), ss = bf2f(f2bf(ps[j]));
-            const float x1 = bf2f(a[j]), x2 = bf2f(bb[j]);
-            a[j] = f2bf(x1 * cc - x2 * ss); bb[j] = f2bf(x2 * cc + x1 * ss);
-        }
+        ecgb::rope_pair<false>(a, bb, A.cs + (size_t)b * half + c * 8, A.sn + (size_t)b * half + c * 8);
         unsigned short *dst = h < G ? s_q[h] : s_k;
         *reinterpret_cast<bf16x8 *>(dst + c * 8) = a;
         *reinterpret_cast<bf16x8 *>(dst + half + c * 8) = bb;
@@ -449,7 +447,7 @@ __global__ __launch_bounds__(kAttnThreads) void decode_attn_scores_kernel(AttnAr
     for (int h = 0; h < kAttnMaxG; ++h)
 #pragma unroll
         for (int t = 0; t < EPL; ++t) qf[h][t] = h < G ? bf2f(s_q[h][lane * EPL + t]) : 0.f;
-    float kn[EPL];
+    float kn[EPL];                                                         // the new key: out of registers (its cache row is being written by another workgroup)
 #pragma unroll
     for (int t = 0; t < EPL; ++t) kn[t] = bf2f(s_k[lane * EPL + t]);
     const unsigned short *K = A.cache + (long long)b * A.cap * width + (long long)g * D;
@@ -458,55 +456,20 @@ __global__ __launch_bounds__(kAttnThreads) void decode_attn_scores_kernel(AttnAr
 #pragma unroll
     for (int h = 0; h < kAttnMaxG; ++h) m[h] = -INFINITY;
     for (int j0 = k0 + wave; j0 < k1; j0 += KU * NW) {
-        float kf[KU][EPL], mk[KU];
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const int j = min(j0 + u * NW, k1 - 1);
-            mk[u] = mrow[j];
-            if (j == len - 1) {                                            // the new key: out of registers (its cache row is being written by another workgroup)
-#pragma unroll
-                for (int t = 0; t < EPL; ++t) kf[u][t] = kn[t];
-            } else {
-                const unsigned short *kr = K + (long long)j * width + lane * EPL;
-                if constexpr (EPL == 4) {
-                    const uint2 kv = *reinterpret_cast<const uint2 *>(kr);
-                    kf[u][0] = __uint_as_float(kv.x << 16); kf[u][1] = __uint_as_float(kv.x & 0xFFFF0000u);
-                    kf[u][2] = __uint_as_float(kv.y << 16); kf[u][3] = __uint_as_float(kv.y & 0xFFFF0000u);
-                } else if constexpr (EPL == 2) {
-                    const unsigned kv = *reinterpret_cast<const unsigned *>(kr);
-                    kf[u][0] = __uint_as_float(kv << 16); kf[u][1] = __uint_as_float(kv & 0xFFFF0000u);
-                } else {
-                    kf[u][0] = bf2f(kr[0]);
-                }
-            }
-        }
+        uint2 kr[KU];
+        float mk[KU];
+        da::load_keys<D, NW, KU>(kr, mk, K, width, mrow, j0, k1, lane);
 #pragma unroll
         for (int h = 0; h < kAttnMaxG; ++h) {
             if (h < G) {
                 float part[KU];
-#pragma unroll
-                for (int u = 0; u < KU; ++u) {
-                    if constexpr (EPL == 4) part[u] = qf[h][0] * kf[u][0] + qf[h][1] * kf[u][1] + qf[h][2] * kf[u][2] + qf[h][3] * kf[u][3];
-                    else if constexpr (EPL == 2) part[u] = qf[h][0] * kf[u][0] + qf[h][1] * kf[u][1];
-                    else part[u] = qf[h][0] * kf[u][0];
-                }
-#pragma unroll
-                for (int d = 32; d > 0; d >>= 1)
-#pragma unroll
-                    for (int u = 0; u < KU; ++u) part[u] += __shfl_xor(part[u], d, 64);
+                da::dot_keys<D, NW, KU, true>(part, qf[h], kr, kn, j0, len - 1);
                 float *srow = A.scores + ((long long)b * A.Hq + g * G + h) * A.cap;
-#pragma unroll
-                for (int u = 0; u < KU; ++u) {
-                    const int j = j0 + u * NW;
-                    if (j < k1) {
-                        const float sdot = (mk[u] != 0.f) ? part[u] * A.scale : -INFINITY;
-                        if (lane == 0) { srow[j] = sdot; s_sc[h][j - k0] = sdot; }
-                        m[h] = fmaxf(m[h], sdot);
-                    }
-                }
+                da::finish_scores<NW, KU>(part, mk, j0, k1, A.scale, lane, m[h], [&](int j, float s) { srow[j] = s; s_sc[h][j - k0] = s; });
             }
         }
     }
+    // da::workgroup_stats head by head, the group's heads sharing its two barriers
 #pragma unroll
     for (int h = 0; h < kAttnMaxG; ++h)
         if (h < G && lane == 0) s_red[h][wave] = m[h];
@@ -514,33 +477,20 @@ __global__ __launch_bounds__(kAttnThreads) void decode_attn_scores_kernel(AttnAr
 #pragma unroll
     for (int h = 0; h < kAttnMaxG; ++h) {
         if (h < G) {
-            float mm = s_red[h][0];
-#pragma unroll
-            for (int w = 1; w < NW; ++w) mm = fmaxf(mm, s_red[h][w]);
-            float l = 0.f;
-            for (int j = k0 + tid; j < k1; j += kAttnThreads) l += (mm == -INFINITY) ? 0.f : __expf(s_sc[h][j - k0] - mm);
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) l += __shfl_xor(l, d, 64);
+            const float l = da::exp_sum_wave<kAttnThreads, false>(s_sc[h], k1 - k0, da::max_of_waves<NW>(s_red[h]), tid);
             if (lane == 0) s_red[h][NW + wave] = l;
-            m[h] = mm;
         }
     }
     __syncthreads();
     if (tid < G) {
-        float l = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) l += s_red[tid][NW + w];
-        float mm = s_red[tid][0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) mm = fmaxf(mm, s_red[tid][w]);
         float *st = A.stats + (((long long)b * A.Hq + g * G + tid) * gridDim.x + sp) * 2;
-        st[0] = mm;
-        st[1] = l;
+        st[0] = da::max_of_waves<NW>(s_red[tid]);
+        st[1] = da::sum_of_waves<NW>(s_red[tid] + NW);
     }
 }
 
-// 3: softmax over the splits' statistics, P.V of the split's keys for every head of the group (attn_decode_values_kernel's sums), and -- the workgroup of a (group,
-// sequence) that takes the last ticket -- the sum of the splits' partial outputs in split order (attn_decode_combine_kernel).  grid (splits, Hkv, B).
+// 3: softmax over the splits' statistics, P.V of the split's keys for every head of the group (a value batch is loaded once for the group), and -- the workgroup of a
+// (group, sequence) that takes the last ticket -- the sum of the splits' partial outputs in split order.  grid (splits, Hkv, B).
 template <int D>
 __global__ __launch_bounds__(kAttnThreads) void decode_attn_values_kernel(AttnArgs2 A)
 {
@@ -564,14 +514,7 @@ __global__ __launch_bounds__(kAttnThreads) void decode_attn_values_kernel(AttnAr
 #pragma unroll
     for (int h = 0; h < kAttnMaxG; ++h) {
         mx[h] = -INFINITY; inv[h] = 0.f;
-        if (h < G) {
-            const float *st = s_st[h];
-            float m = -INFINITY;
-            for (int t = 0; t < n_splits; ++t) m = fmaxf(m, st[2 * t]);
-            float l = 0.f;
-            for (int t = 0; t < n_splits; ++t) l += (st[2 * t] == -INFINITY) ? 0.f : st[2 * t + 1] * __expf(st[2 * t] - m);
-            mx[h] = m; inv[h] = l > 0.f ? 1.f / l : 0.f;
-        }
+        if (h < G) da::merge_splits(s_st[h], n_splits, mx[h], inv[h]);
     }
     float acc[kAttnMaxG][8];
 #pragma unroll
@@ -579,6 +522,7 @@ __global__ __launch_bounds__(kAttnThreads) void decode_attn_values_kernel(AttnAr
 #pragma unroll
         for (int t = 0; t < 8; ++t) acc[h][t] = 0.f;
     for (int j0 = k0 + slice; j0 < k1; j0 += VU * NS) {
+        // da::load_values + da::pv_batch, written out: through the routines this loop takes 139 registers instead of 120 (three waves a SIMD instead of four)
         bf16x8 vv[VU];
 #pragma unroll
         for (int u = 0; u < VU; ++u) vv[u] = *reinterpret_cast<const bf16x8 *>(V + (long long)min(j0 + u * NS, k1 - 1) * width + piece * 8);
@@ -589,25 +533,16 @@ __global__ __launch_bounds__(kAttnThreads) void decode_attn_values_kernel(AttnAr
 #pragma unroll
                 for (int u = 0; u < VU; ++u) {
                     const int j = j0 + u * NS;
-                    const float sc = srow[min(j, k1 - 1)];
-                    const float e = (mx[h] == -INFINITY) ? 0.f : __expf(sc - mx[h]);
-                    const float pj = (j < k1) ? bf2f(f2bf(e * inv[h])) : 0.f;
+                    const float pj = (j < k1) ? da::bf_value(da::bf_bits(da::exp_or_zero(srow[min(j, k1 - 1)], mx[h]) * inv[h])) : 0.f;
 #pragma unroll
-                    for (int t = 0; t < 8; ++t) acc[h][t] += pj * bf2f(vv[u][t]);
+                    for (int t = 0; t < 8; ++t) acc[h][t] += pj * da::bf_value(vv[u][t]);
                 }
             }
         }
     }
     for (int h = 0; h < G; ++h) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) s_part[slice * D + piece * 8 + t] = acc[h][t];
-        __syncthreads();
-        if (tid < D) {
-            float sum = 0.f;
-#pragma unroll
-            for (int sl = 0; sl < NS; ++sl) sum += s_part[sl * D + tid];
-            A.partial[(((long long)b * A.Hq + g * G + h) * n_splits + sp) * D + tid] = sum;
-        }
+        const float sum = da::slice_sum<D, kAttnThreads>(acc[h], s_part, tid);
+        if (tid < D) A.partial[(((long long)b * A.Hq + g * G + h) * n_splits + sp) * D + tid] = sum;
         __syncthreads();
     }
     // ---- the last workgroup of the (group, sequence) to get here adds the splits in order
@@ -619,15 +554,7 @@ __global__ __launch_bounds__(kAttnThreads) void decode_attn_values_kernel(AttnAr
     for (int i = tid; i < G * D; i += kAttnThreads) {
         const int h = i / D, d = i % D;
         const float *p = A.partial + ((long long)b * A.Hq + g * G + h) * n_splits * D + d;
-        float sum = 0.f;
-        for (int t0 = 0; t0 < n_splits; t0 += 16) {              // sixteen splits' values in flight, added in split order
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = p[(long long)min(t0 + u, n_splits - 1) * D];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) if (t0 + u < n_splits) sum += v[u];
-        }
-        A.o[((long long)b * A.Hq + g * G + h) * D + d] = f2bf(sum);
+        A.o[((long long)b * A.Hq + g * G + h) * D + d] = da::bf_bits(da::combine_splits(n_splits, [&](int t) { return p[(long long)t * D]; }));
     }
     if (tid == 0) A.tickets[b * A.Hkv + g] = 0u;               // ready for the next launch (a replayed graph never clears the buffer itself)
 }

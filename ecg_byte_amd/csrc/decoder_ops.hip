@@ -15,6 +15,7 @@
 #include <string>
 
 #include "glu_math.hpp"
+#include "rope_math.hpp"
 #include "tokenizer.hpp"
 
 namespace {
@@ -490,7 +491,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_rows_kernel(const unsigned sh
 
 // ---- RoPE --------------------------------------------------------------------------------------
 // x: [T, n_heads, D] (token-major, heads contiguous); cos/sin: [T, D/2] fp32.  In place.
-// forward:  (x1, x2) -> (x1*c - x2*s, x2*c + x1*s);  backward (INVERSE): (g1*c + g2*s, g2*c - g1*s)
+// forward:  (x1, x2) -> (x1*c - x2*s, x2*c + x1*s);  backward (INVERSE): (g1*c + g2*s, g2*c - g1*s)   (ecgb::rope_pair)
 template <bool INVERSE>
 __global__ __launch_bounds__(256) void rope_kernel(unsigned short *x, const float *cs, const float *sn, size_t T,
                                                    int n_heads, int D, size_t row_stride)
@@ -505,15 +506,7 @@ __global__ __launch_bounds__(256) void rope_kernel(unsigned short *x, const floa
         const size_t t = th / n_heads;
         unsigned short *p = x + t * row_stride + (size_t)h * D + c * 8;
         bf16x8 a = *reinterpret_cast<bf16x8 *>(p), b = *reinterpret_cast<bf16x8 *>(p + half);
-        const float *pc = cs + t * half + c * 8, *ps = sn + t * half + c * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            // HF holds cos/sin in the activation dtype (bf16): modeling_llama.py:163-165
-            const float cc = bf2f(f2bf(pc[j])), ss = bf2f(f2bf(ps[j]));
-            const float x1 = bf2f(a[j]), x2 = bf2f(b[j]);
-            if (!INVERSE) { a[j] = f2bf(x1 * cc - x2 * ss); b[j] = f2bf(x2 * cc + x1 * ss); }
-            else { a[j] = f2bf(x1 * cc + x2 * ss); b[j] = f2bf(x2 * cc - x1 * ss); }
-        }
+        ecgb::rope_pair<INVERSE>(a, b, cs + t * half + c * 8, sn + t * half + c * 8);
         *reinterpret_cast<bf16x8 *>(p) = a;
         *reinterpret_cast<bf16x8 *>(p + half) = b;
     }
@@ -534,13 +527,7 @@ __global__ __launch_bounds__(256) void rope_append_kernel(unsigned short *qkv, c
             const int c = i % per_head, th = i / per_head, h = th % (n_q + n_kv), t = th / (n_q + n_kv);
             unsigned short *p = qkv + (size_t)t * row_stride + (size_t)h * D + c * 8;
             bf16x8 a = *reinterpret_cast<bf16x8 *>(p), b = *reinterpret_cast<bf16x8 *>(p + half);
-            const float *pc = cs + (size_t)t * half + c * 8, *ps = sn + (size_t)t * half + c * 8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float cc = bf2f(f2bf(pc[j])), ss = bf2f(f2bf(ps[j]));
-                const float x1 = bf2f(a[j]), x2 = bf2f(b[j]);
-                a[j] = f2bf(x1 * cc - x2 * ss); b[j] = f2bf(x2 * cc + x1 * ss);
-            }
+            ecgb::rope_pair<false>(a, b, cs + (size_t)t * half + c * 8, sn + (size_t)t * half + c * 8);
             *reinterpret_cast<bf16x8 *>(p) = a;
             *reinterpret_cast<bf16x8 *>(p + half) = b;
             if (h >= n_q) {
