@@ -181,6 +181,8 @@ def lib():
         "ecgb_attn_decode_split": [vp, vp, vp, ll, ll, vp, ll, vp, ci, ci, ci, ci, ci, f32, ci, vp, sz, vp],
         "ecgb_kv_append": [vp, ll, ll, ci, vp, ll, ci, vp, vp],
         "ecgb_argmax_bf16": [vp, ll, ci, ci, vp, vp],
+        "ecgb_sample_bf16": [vp, ll, ci, ci, f32, ci, f32, vp, vp, ci, vp, vp, sz, vp, vp],
+        "ecgb_philox4x32_10": [u32p, u32p, u32p],
         "ecgb_decode_advance": [vp, ci, vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, ci, vp],
         "ecgb_decode_advance_e": [vp, ci, vp, vp, vp, vp, vp, ll, vp, ll, vp, ll, vp, ci, vp, vp],
         "ecgb_gemm_nt_bf16_lora_decode": [vp, ll, vp, ll, vp, ll, f32, vp, ll, ci, vp, vp, ll, ci, ci, ci, vp, vp],
@@ -232,6 +234,8 @@ def lib():
     for name in ("ecgb_layernorm_bwd_scratch_floats", "ecgb_colsum_scratch_floats"):
         getattr(L, name).argtypes = [sz, ci]
         getattr(L, name).restype = sz
+    L.ecgb_sample_scratch_bytes.argtypes = [ci]
+    L.ecgb_sample_scratch_bytes.restype = sz
     L.ecgb_partial_rows_sum_f32.argtypes = [vp, ci, ci, ll, vp, vp]
     L.ecgb_partial_rows_sum_f32.restype = C.c_int
     L.ecgb_decode_attn_scratch_floats.argtypes = [ll, ci, ci, ci, ci, ci]

@@ -1148,13 +1148,18 @@ class HipCausalLM(nn.Module):
 
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=128, pad_token_id=None, eos_token_id=None,
                  use_cache=True, return_logits=False, use_graph=None, do_sample=None, temperature=None, top_k=None, top_p=None,
-                 generator=None, merge_adapters=False, **kw):
-        """merge_adapters=True (opt-in, LoRA models only): the adapters are folded into copies of the projection weights once per call and the decode step runs
+                 generator=None, merge_adapters=False, device_sampler=None, **kw):
+        """device_sampler=True (opt-in, needs do_sample to resolve true): the token is drawn on the device by `ops.sample_rows` (temperature, top-k, top-p and the draw
+        in one launch on the bf16 logits, counter-seeded) instead of torch's topk / sort / softmax / cumsum / multinomial, and the decode step is the replayed graph,
+        captured once and reused across calls and seeds like the greedy one.  Per call one 64-bit nonce is drawn from the torch generator in force (`generator`, or the
+        device's default generator, which torch.manual_seed seeds) and the seed is its initial_seed(): re-seeding reproduces a run, successive calls differ.  Not the
+        tokens of the torch path (another generator; ties at the top-p cut keep the lower ids: include/ecgbyte_decoder.h).
+        merge_adapters=True (opt-in, LoRA models only): the adapters are folded into copies of the projection weights once per call and the decode step runs
         without the five adapter branches per layer -- peft's `merge_and_unload()` for inference.  Not bit-identical to the unmerged step (see `_merged_weights`);
         the reference's own eval loop (ecg_byte/runners/inference.py, main.py:181-195) generates with the adapters unmerged, which stays the default."""
         with self._adapters_merged() if merge_adapters and self.lora is not None else contextlib.nullcontext():
             return self._generate(input_ids, attention_mask, max_new_tokens, pad_token_id, eos_token_id, use_cache, return_logits, use_graph, do_sample,
-                                  temperature, top_k, top_p, generator)
+                                  temperature, top_k, top_p, generator, device_sampler)
 
     @contextlib.contextmanager
     def _adapters_merged(self):
@@ -1176,7 +1181,7 @@ class HipCausalLM(nn.Module):
 
     def _generate(self, input_ids=None, attention_mask=None, max_new_tokens=128, pad_token_id=None, eos_token_id=None,
                   use_cache=True, return_logits=False, use_graph=None, do_sample=None, temperature=None, top_k=None, top_p=None,
-                  generator=None):
+                  generator=None, device_sampler=None):
         """GenerationMixin.generate / _sample (generation/utils.py:1877, 3131-3250) as LLM.generate calls it
         (ecg_byte/models/llm.py:26-37): positions from the attention mask (utils.py:410-411), finished sequences keep emitting
         pad_token_id, stop when every sequence has produced eos_token_id or after max_new_tokens.  Greedy unless do_sample: the
@@ -1184,7 +1189,7 @@ class HipCausalLM(nn.Module):
         the Llama-3.2 conversion writes with do_sample=True, temperature 0.6, top_p 0.9 (convert_llama_weights_to_hf.py:402-408);
         `from_pretrained` reads that file into `self.generation_config` and the arguments default to it.
         use_graph: None (default) = the decode step runs as a replayed HIP graph (`_generate_graph`) whenever nothing asks for the eager loop
-        (per-step logits, no cache, sampling); True / False force it.
+        (per-step logits, no cache, sampling by torch); True / False force it.  device_sampler: see `generate`.
         Returns [B, S0 + generated] int64 (prompt included)."""
         gc = getattr(self, "generation_config", None) or {}
         do_sample = bool(gc.get("do_sample", False)) if do_sample is None else bool(do_sample)
@@ -1192,10 +1197,16 @@ class HipCausalLM(nn.Module):
         top_k = int(gc.get("top_k", 50)) if top_k is None else int(top_k)                    # GenerationConfig's defaults
         top_p = float(gc.get("top_p", 1.0)) if top_p is None else float(top_p)
         V = self.cfg.vocab_size
-        if do_sample:
-            pick = lambda lg16: self._next_token(lg16[:, :V].float(), True, temperature, top_k, top_p, generator)
+        device_sampler = bool(device_sampler)
+        if device_sampler and not do_sample:
+            raise ValueError("device_sampler=True needs do_sample (the argument, or the checkpoint's generation_config.json)")
+        # pick(bf16 logits as the head GEMM leaves them, tokens present) -> [B] int64
+        if device_sampler:
+            pick = None                                         # made where its scratch and seed words live: below for the eager loop, in _generate_graph for the graph
+        elif do_sample:
+            pick = lambda lg16, step=None: self._next_token(lg16[:, :V].float(), True, temperature, top_k, top_p, generator)
         else:
-            pick = lambda lg16: ops.argmax_rows(lg16, V)        # the bf16 logits as the head GEMM leaves them: one launch, first maximum (torch.argmax's rule)
+            pick = lambda lg16, step=None: ops.argmax_rows(lg16, V)        # one launch, first maximum (torch.argmax's rule)
         c = self.cfg
         dev = self.device
         input_ids = input_ids.to(dev).long()
@@ -1214,10 +1225,15 @@ class HipCausalLM(nn.Module):
             return p.masked_fill(m == 0, 1)
 
         if use_graph is None:
-            use_graph = generator is None and not do_sample          # (sampling replays too when asked: use_graph=True)
+            use_graph = device_sampler or (generator is None and not do_sample)          # (torch's sampling replays too when asked: use_graph=True)
         if use_cache and use_graph and not return_logits and max_new_tokens > 2:
             return self._generate_graph(input_ids, mask, S0, max_new_tokens, pad_token_id, eos, positions, pick,
-                                        (do_sample, temperature, top_k, top_p) if do_sample else None)
+                                        (do_sample, temperature, top_k, top_p) if do_sample else None, device_sampler, generator)
+        sampler_scratch = None
+        if device_sampler:
+            seed2, sampler_scratch = torch.empty(2, dtype=torch.int64, device=dev), ops.sample_scratch(B, dev)
+            self._seed_sampler(seed2, generator)
+            pick = lambda lg16, step: ops.sample_rows(lg16, V, temperature, top_k, top_p, seed2, step, sampler_scratch)
         width = 2 * c.num_key_value_heads * c.head_dim
         cap_rows = -(-cap // 128) * 128                                   # as _generate_graph sizes them: the same split of the keys, the same bits
         caches = [torch.empty((B, cap_rows, width), dtype=torch.bfloat16, device=dev) for _ in range(c.num_hidden_layers)] if use_cache else None
@@ -1238,7 +1254,9 @@ class HipCausalLM(nn.Module):
             logits = ops.gemm_nt(last, self.embed.data)
             if return_logits:
                 step_logits.append(logits[:, :c.vocab_size].float())
-            nxt = pick(logits)
+            nxt = pick(logits, n)
+            if sampler_scratch is not None:
+                ops.sample_check(sampler_scratch)
             if eos is not None:
                 nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
             seq = torch.cat([seq, nxt[:, None]], 1)
@@ -1249,15 +1267,27 @@ class HipCausalLM(nn.Module):
                     break
         return (seq, torch.stack(step_logits, 1)) if return_logits else seq
 
-    def _generate_graph(self, seq, mask, S0, max_new_tokens, pad_token_id, eos, positions, pick, sampling=None):
+    def _seed_sampler(self, seed2, generator):
+        """The device sampler's words of one generate call, into seed2 (int64[2] on the device): the initial_seed() of the torch generator in force and one 64-bit
+        nonce drawn from it (no host synchronisation)."""
+        dev = seed2.device
+        gen = generator if generator is not None else torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
+        seed = int(gen.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        nonce = torch.empty(1, dtype=torch.int64, device=gen.device).random_(generator=gen)
+        seed2[0:1].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)
+        seed2[1:2].copy_(nonce, non_blocking=True)
+
+    def _generate_graph(self, seq, mask, S0, max_new_tokens, pad_token_id, eos, positions, pick, sampling=None, device_sampler=False, generator=None):
         """The generate loop with the decode step captured once in a HIP graph and replayed per token.  Everything that changes from step to
         step lives in device memory -- the token, its position, the number of valid cache rows, the column the next token goes to, the
         `unfinished` flags -- so the host only replays and, when an eos id is given, reads one flag per token.
         The captured step is kept on the model and REUSED by later calls (`self._gen_graphs`): its buffers (KV caches, mask, output) are sized
         to the call's prompt + new tokens rounded up to 128 rows, so the eval loop's calls (one per test sample, prompts of different lengths,
         ecg_byte/runners/tester.py) replay one graph; a call writes its prompt state into the buffers and replays.  Key: batch, rounded
-        capacity, pad / eos ids, the sampling arguments, and the storage of the embedding table and of the adapters (a resized vocabulary
-        or enable_lora() captures anew).  At Gemma-2B dims with adapters (about 400 launches per token, which the host issues at 8 us each):
+        capacity, pad / eos ids, the sampling arguments, whether the device sampler draws (its step is cached like the greedy one: the sampling
+        arguments are kernel arguments of the capture, its scratch and seed words live in the cached state and every call writes seed and nonce
+        into them before the first pick; the step number is `n_dev`, which the step advances itself), and the storage of the embedding table and
+        of the adapters (a resized vocabulary or enable_lora() captures anew).  At Gemma-2B dims with adapters (about 400 launches per token, which the host issues at 8 us each):
         3.5 ms per token eagerly, 2.25 replayed (423 tokens/s after a 600-token prompt; 530 without adapters); capturing costs about 16 ms, once.
         The greedy choice inside the step is ecgb_argmax_bf16, not torch.argmax: over a 260 000-wide row torch's reduction is two passes over a
         semaphore buffer, and a graph holding it, replayed after other eager reductions had run, left the token unwritten (measured: the second
@@ -1269,8 +1299,11 @@ class HipCausalLM(nn.Module):
         pad_id = pad_token_id if pad_token_id is not None else 0
         key = (B, cap, pad_id, None if eos is None else tuple(int(e) for e in eos.tolist()), sampling, self.training, self.embed.data_ptr(),
                None if self.lora is None else self.lora[0]["qkv"].A.data_ptr(), self.wqkv[0].data_ptr(), bool(self.decode_attn_one), bool(self.decode_lora_one))      # (the last: base weights or their merged copies)
+        if device_sampler:
+            key = key + (True,)
+        reuse = sampling is None or device_sampler                           # (torch's sampling step holds its sort / cumsum / multinomial: captured per call)
         graphs = self.__dict__.setdefault("_gen_graphs", {})
-        st = graphs.get(key) if sampling is None else None                   # (a sampling step holds torch's sort / cumsum / multinomial: captured per call, see below)
+        st = graphs.get(key) if reuse else None
         if st is None:
             while len(graphs) >= 4:                                          # a handful of shapes at most: drop the oldest
                 graphs.pop(next(iter(graphs)))
@@ -1290,9 +1323,15 @@ class HipCausalLM(nn.Module):
                 st.scratch_one = ops.decode_one_scratch(B, c.num_attention_heads, c.head_dim, ns, dev)
             elif ns > 1:
                 st.scratch = ops.decode_split_scratch(cap, B, c.num_attention_heads, c.head_dim, ns, dev)
-            if sampling is None:
+            if device_sampler:
+                st.seed2, st.sample_scratch = torch.empty(2, dtype=torch.int64, device=dev), ops.sample_scratch(B, dev)
+            if reuse:
                 graphs[key] = st
         caches, gmask, out, tok, pos, n_dev, col, unfinished = st.caches, st.mask, st.out, st.tok, st.pos, st.n_dev, st.col, st.unfinished
+        if device_sampler:
+            V, (_, temperature, top_k, top_p) = c.vocab_size, sampling
+            self._seed_sampler(st.seed2, generator)
+            pick = lambda lg16, step: ops.sample_rows(lg16, V, temperature, top_k, top_p, st.seed2, step, st.sample_scratch)
         # prefill + first token, eagerly
         gmask.zero_()
         gmask[:, :S0] = mask[:, :S0]
@@ -1300,7 +1339,7 @@ class HipCausalLM(nn.Module):
         hf = self._hidden_states(seq, m0, positions(m0), caches)
         logits = ops.gemm_nt(hf.view(B, S0, -1)[:, -1].contiguous(), self.embed.data)
         unfinished.fill_(1)
-        nxt = pick(logits)
+        nxt = pick(logits, S0)
         if eos is not None:
             unfinished.mul_((~torch.isin(nxt, eos)).long())
         out.fill_(pad_id)
@@ -1308,6 +1347,8 @@ class HipCausalLM(nn.Module):
         out[:, S0] = nxt
         gmask[:, S0] = 1.0
         if (eos is not None and int(unfinished.max()) == 0) or max_new_tokens == 1:
+            if device_sampler:
+                ops.sample_check(st.sample_scratch)
             return out[:, :S0 + 1].clone()
         # state of the captured step
         tok.copy_(nxt)
@@ -1321,7 +1362,7 @@ class HipCausalLM(nn.Module):
         def step():
             one = self.lora is not None and not self.training and self.decode_lora_one
             last = self._decode_step(tok, pos, gmask, caches, None, n_dev, scratch=st.scratch, scratch_one=st.scratch_one, epoch_advanced=one)
-            nx = pick(ops.gemm_nt(last, self.embed.data))
+            nx = pick(ops.gemm_nt(last, self.embed.data), n_dev)      # (n_dev: the tokens present, as `n` in the eager loop)
             # pad for finished sequences, the eos test, the token into `out` and `tok`, the mask's new column, the three counters: one launch (six to eleven
             # element-wise ones before, 5 us each in the replayed graph)
             ops.decode_advance_(nx.to(torch.int64), tok, pos, col, n_dev, out, gmask, unfinished, pad_id, eos_i64, epoch=self._decode_epoch(dev) if one else None)
@@ -1348,6 +1389,8 @@ class HipCausalLM(nn.Module):
             produced += 1
             if eos is not None and int(unfinished.max()) == 0:
                 break
+        if device_sampler:
+            ops.sample_check(st.sample_scratch)                              # a row with nothing to draw in any step of the call
         return out[:, :S0 + produced].clone()
 
     # ---- backward -------------------------------------------------------------------------------

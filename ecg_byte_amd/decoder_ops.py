@@ -165,6 +165,39 @@ def argmax_rows(x, n=None):
     return out
 
 
+def sample_scratch(rows, device):
+    """The scratch of one call site of `sample_rows` (ecgb_sample_scratch_bytes), zeroed: word 0 is the "a row had nothing to draw" flag."""
+    return torch.zeros((_L().ecgb_sample_scratch_bytes(int(rows)) + 3) // 4, dtype=torch.int32, device=device)
+
+
+def sample_rows(x, n, temperature, top_k, top_p, seed2, step, scratch, u=None):
+    """One token per row of the bf16 logits x[:, :n] after temperature, top-k and top-p, drawn in one launch (ecgb_sample_bf16; the rule: include/ecgbyte_decoder.h).
+    seed2: int64[2] on the device (seed, per-call nonce); step: an int, or an int32[1] device tensor the decode step advances (a replayed graph); the uniform of row r
+    is Philox4x32-10 of (seed, nonce, r, step).  u: float64[rows] in [0, 1) used instead (tests).  scratch: `sample_scratch(rows)`, owned by the call site; a row with
+    nothing drawable gives token 0 and raises its flag -- see `sample_check`."""
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1 and scratch.dtype == torch.int32
+    rows = x.shape[0]
+    n = x.shape[1] if n is None else int(n)
+    assert seed2 is None or (seed2.dtype == torch.int64 and seed2.numel() == 2 and seed2.is_contiguous())
+    assert u is None or (u.dtype == torch.float64 and u.numel() == rows and u.is_contiguous())
+    step_dev = None
+    if torch.is_tensor(step):
+        assert step.dtype == torch.int32 and step.numel() == 1
+        step_dev, step = step, 0
+    out = torch.empty(rows, dtype=torch.int64, device=x.device)
+    _lib.check(_L().ecgb_sample_bf16(_p(x), x.stride(0), rows, n, float(temperature), int(top_k), float(top_p), _p(seed2), _p(step_dev), int(step), _p(u),
+                                     _p(scratch), scratch.numel() * 4, _p(out), _st()))
+    return out
+
+
+def sample_check(scratch):
+    """Raise if a `sample_rows` call on this scratch met a row with nothing drawable (only NaN / -inf); the flag is cleared.  Reads one word: synchronises."""
+    flag = int(scratch[0])
+    if flag:
+        scratch[0] = 0
+        raise RuntimeError("sample_rows: a row of logits has no drawable entry (only NaN / -inf)" if flag == 1 else f"sample_rows: internal error {flag}")
+
+
 def embed_bwd_sorted_(ids, dout, grad_table_bf16, scale=1.0, skip_id=-1):
     """grad_table_bf16[id] += scale * sum of dout rows with that id, in place, no atomics (ecgb_embed_bwd_sorted): the same bits every call."""
     flat = ids.reshape(-1)

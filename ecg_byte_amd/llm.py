@@ -25,7 +25,8 @@ class LLM(nn.Module):
         input_len = batch["tokenized_signal"].shape[1]
         generated_ids = self.llm.generate(input_ids=batch["tokenized_signal"].to(dev), attention_mask=batch["attn_mask"].to(dev),
                                           max_new_tokens=128, pad_token_id=tokenizer.pad_token_id,
-                                          eos_token_id=tokenizer.eos_token_id, use_cache=True)
+                                          eos_token_id=tokenizer.eos_token_id, use_cache=True,
+                                          device_sampler=getattr(self.args, "device_sampler", None))
         return tokenizer.batch_decode(generated_ids[:, input_len:], skip_special_tokens=True,
                                       clean_up_tokenization_spaces=False)[0]
 

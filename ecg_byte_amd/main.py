@@ -63,6 +63,8 @@ def get_args(argv=None):
     p.add_argument("--data_root", type=str, default="./data")
     p.add_argument("--runs_root", type=str, default="./runs")
     p.add_argument("--workers", type=int, default=4, help="reader threads of the batch loader")
+    p.add_argument("--device_sampler", action="store_true",
+                   help="inference with a sampling checkpoint: draw the token on the device inside the replayed decode step (HipCausalLM.generate(device_sampler=True))")
     return p.parse_args(argv)
 
 

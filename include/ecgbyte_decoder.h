@@ -402,6 +402,29 @@ int ecgb_rope_append(void *qkv_dev, const float *cos_dev, const float *sin_dev, 
  * out[r] = index of the first maximum of the bf16 row x[r, 0:n] (rows `ld` elements apart).  One launch, no workspace. */
 int ecgb_argmax_bf16(const void *x_dev, long long ld, int rows, int n, int64_t *out_dev, void *stream);
 
+/* Sampling token choice of generate() (GenerationMixin._sample with do_sample: TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> softmax ->
+ * torch.multinomial; generation/utils.py:3131-3250, generation/logits_process.py) in ONE launch, deterministic and counter-seeded (csrc/sample.hip), so that a sampling
+ * decode step is a graph captured once.  out[r] in [0, n) for every bf16 row x[r, 0:n] (rows `ld` elements apart; columns n..ld are never read as candidates).
+ * The rule, in exact arithmetic, evaluated in float64 (tests/sample_ref.py restates it per token):
+ *   1. -0 is +0.  NaN and -inf entries are never drawn.  If +inf is present, the +inf entries have weight 1 and all others weight 0.
+ *   2. The drawable entries are ordered by value descending, then token id ascending.
+ *   3. top_k (0 or >= n: off) keeps every entry whose value is >= the k-th largest value, ties included (HF's `scores < kth` test).
+ *   4. w_i = exp((x_i - x_max) / temperature), Z = the sum over the entries step 3 kept.  top_p keeps an entry iff the weight of the entries ordered before it is
+ *      < top_p * Z; the first entry is always kept.  (HF's `cumsum(ascending softmax) <= 1 - top_p` removal with min_tokens_to_keep = 1, from the other end; where a
+ *      tie straddles the cut torch's unstable sort picks arbitrarily and this rule keeps the lower ids.)
+ *   5. With Z' the kept weight and u in [0, 1), the drawn token is the first kept entry, in that order, whose inclusive cumulative weight is > u * Z'; if rounding
+ *      would overshoot, the last kept entry.
+ *   6. A row with nothing drawable writes token 0 and sets the int32 word at scratch_dev[0] to a non-zero value; the kernel never clears it (the caller does).
+ * u: u_dev[r] when u_dev is given (tests), else from Philox4x32-10 with key = (seed lo, seed hi), counter = (r, step, nonce lo, nonce hi):
+ * u = (((uint64) out0 << 32 | out1) >> 11) * 2^-53.  seed_dev[0] = seed, seed_dev[1] = a per-call nonce; step = *step_dev when step_dev is given (a word the replayed decode
+ * step already advances), else the argument.  Nothing is incremented on the device.  The same inputs give the same token on every launch (no float atomics).
+ * temperature > 0; 0 < top_p <= 1; top_k >= 0; n <= 2^25.  scratch_dev: ecgb_sample_scratch_bytes(rows) bytes owned by the call site, zero before the first call. */
+size_t ecgb_sample_scratch_bytes(int rows);
+int ecgb_sample_bf16(const void *x_dev, long long ld, int rows, int n, float temperature, int top_k, float top_p, const uint64_t *seed_dev, const int *step_dev, int step,
+                     const double *u_dev, void *scratch_dev, size_t scratch_bytes, int64_t *out_dev, void *stream);
+/* The generator's block function on the host (Philox4x32-10, ten rounds; Random123's known-answer vectors): for tests. */
+int ecgb_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+
 /* The RoPE table rows of a decode step: cos_out / sin_out [n, half] (fp32) = cos / sin of float(pos[i]) * inv_freq[j], the fp32 product rounded once -- the bits of
  * `fr = pos.float()[:, None] * inv_freq[None, :]; fr.cos(), fr.sin()` (LlamaRotaryEmbedding.forward, modeling_llama.py:119-139, in fp32), one launch instead of four. */
 int ecgb_rope_table(const int64_t *pos_dev, int n, const float *inv_freq_dev, int half, float *cos_out_dev, float *sin_out_dev, void *stream);
