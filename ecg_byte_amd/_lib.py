@@ -59,6 +59,20 @@ def lib():
     L.ecgb_tokenizer_copy_nodes.restype = sz
     L.ecgb_tokenizer_copy_runbits.argtypes = [vp, u32p, sz]
     L.ecgb_tokenizer_copy_runbits.restype = sz
+    L.ecgb_tokenizer_copy_expansions.argtypes = [vp, u32p, u32p, sz, C.POINTER(C.c_uint8), sz]
+    L.ecgb_tokenizer_copy_expansions.restype = sz
+    L.ecgb_tokenizer_expansion_bytes.argtypes = [vp]
+    L.ecgb_tokenizer_expansion_bytes.restype = sz
+    L.ecgb_detokenize_hip.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp]
+    L.ecgb_detokenize_hip.restype = C.c_int
+    L.ecgb_detokenize_values_f32_hip.argtypes = [vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp]
+    L.ecgb_detokenize_values_f32_hip.restype = C.c_int
+    L.ecgb_detokenize_signal_f64_hip.argtypes = [vp, vp, sz, vp, sz, C.c_double, C.c_double, vp, sz, vp, vp, vp, sz, vp, vp, vp]
+    L.ecgb_detokenize_signal_f64_hip.restype = C.c_int
+    L.ecgb_token_histogram_hip.argtypes = [vp, sz, vp, sz, vp, sz, vp, vp]
+    L.ecgb_token_histogram_hip.restype = C.c_int
+    L.ecgb_detokenize_tile.argtypes = [u32p, u32p]
+    L.ecgb_detokenize_tile.restype = None
     L.ecgb_quantize_hip.argtypes = [vp, sz, C.c_double, C.c_double, vp, vp, vp]
     L.ecgb_quantize_hip.restype = C.c_int
     L.ecgb_encode_scratch_bytes.argtypes = [vp, sz, sz]

@@ -95,6 +95,55 @@ void build_general(ecgb_tokenizer *tok, const uint32_t *flat_bytes, const uint32
     tok->nodes.clear(); tok->runbits.clear(); tok->tok_len.clear();
 }
 
+// The expansion table of tokenizer.hpp: which entry of the list owns each id first (the last one that names it), then the bytes of the owners in list order.
+void build_expansions(ecgb_tokenizer *tok, const uint32_t *flat_bytes, const uint32_t *offsets, const uint32_t *ids, size_t n_merges)
+{
+    uint32_t max_id = 255;
+    for (size_t i = 0; i < n_merges; ++i) max_id = std::max(max_id, ids[i]);
+    if (max_id >= ecgb::kMaxExpansionIds) return;
+    const size_t n_ids = (size_t)max_id + 1;
+    std::vector<int64_t> owner(n_ids, -1);                 // list index of the entry that defines the id; -1 = none (ids 0..255: the byte itself)
+    for (size_t i = 0; i < n_merges; ++i) owner[ids[i]] = (int64_t)i;
+    tok->exp_tab.assign(2 * n_ids, 0u);
+    tok->exp_bytes.resize(256);
+    for (uint32_t b = 0; b < 256; ++b) {
+        tok->exp_bytes[b] = (uint8_t)b;
+        if (owner[b] < 0) { tok->exp_tab[2 * b] = b; tok->exp_tab[2 * b + 1] = 1; }
+    }
+    tok->exp_max_len = 1;
+    for (size_t i = 0; i < n_merges; ++i) {
+        if (owner[ids[i]] != (int64_t)i) continue;         // an earlier duplicate: overwritten
+        const uint32_t *seq = flat_bytes + offsets[i];
+        const size_t len = offsets[i + 1] - offsets[i];
+        bool bytes_only = true;
+        for (size_t k = 0; k < len; ++k) bytes_only = bytes_only && seq[k] <= 255u;
+        if (!bytes_only || len == 0) continue;             // length 0: not in the vocabulary
+        tok->exp_tab[2 * (size_t)ids[i]] = (uint32_t)tok->exp_bytes.size();
+        tok->exp_tab[2 * (size_t)ids[i] + 1] = (uint32_t)len;
+        for (size_t k = 0; k < len; ++k) tok->exp_bytes.push_back((uint8_t)seq[k]);
+        tok->exp_max_len = std::max<uint32_t>(tok->exp_max_len, (uint32_t)len);
+    }
+    tok->exp_bytes.resize(tok->exp_bytes.size() + 16, 0);
+    tok->exp_built = true;
+}
+
+// uploads the expansion table beside the trie (either form); called with the device already chosen
+int upload_expansions(ecgb_tokenizer *tok)
+{
+    if (!tok->exp_built) return ECGB_OK;
+    const size_t tb = tok->exp_tab.size() * sizeof(uint32_t), bb = tok->exp_bytes.size();
+    if (hipMalloc((void **)&tok->exp_tab_dev, tb) != hipSuccess || hipMalloc((void **)&tok->exp_bytes_dev, bb) != hipSuccess) {
+        ecgb::set_error("ecgb_tokenizer_create: hipMalloc failed (expansion table)");
+        return ECGB_ERR_NOMEM;
+    }
+    if (hipMemcpy(tok->exp_tab_dev, tok->exp_tab.data(), tb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(tok->exp_bytes_dev, tok->exp_bytes.data(), bb, hipMemcpyHostToDevice) != hipSuccess) {
+        ecgb::set_error("ecgb_tokenizer_create: hipMemcpy failed (expansion table)");
+        return ECGB_ERR_HIP;
+    }
+    return ECGB_OK;
+}
+
 // uploads the general form; the packed form's device pointers stay null except `lut_dev`/`nodes_dev` markers the entry points test
 int upload_general(ecgb_tokenizer *tok)
 {
@@ -113,7 +162,7 @@ int upload_general(ecgb_tokenizer *tok)
         ecgb::set_error("ecgb_tokenizer_create: hipMemcpy failed (general trie)");
         return ECGB_ERR_HIP;
     }
-    return ECGB_OK;
+    return upload_expansions(tok);
 }
 
 }  // namespace
@@ -146,6 +195,7 @@ extern "C" int ecgb_tokenizer_create(const uint32_t *flat_bytes, const uint32_t 
             // prefix in front of it adds (token-less) nodes.
             for (uint32_t k = offsets[i]; k < offsets[i + 1] && flat_bytes[k] <= 255u; ++k) used[flat_bytes[k]] = true;
         }
+        build_expansions(tok, flat_bytes, offsets, ids, n_merges);
         for (uint32_t b = 0; b < 256; ++b) {
             if (!used[b] || tok->byte_to_class[b] != kOtherClass) continue;
             if (n_classes == kMaxClasses) {      // more than 29 distinct byte values (a..z plus 3): the general form
@@ -337,6 +387,8 @@ extern "C" int ecgb_tokenizer_create(const uint32_t *flat_bytes, const uint32_t 
         ecgb::set_error("ecgb_tokenizer_create: hipMemcpy failed");
         return ECGB_ERR_HIP;
     }
+    const int rc_exp = upload_expansions(tok);
+    if (rc_exp) { ecgb_tokenizer_destroy(tok); return rc_exp; }
     *out = tok;
     return ECGB_OK;
 }
@@ -351,6 +403,8 @@ extern "C" void ecgb_tokenizer_destroy(ecgb_tokenizer *tok)
     if (tok->g_keys_dev) (void)hipFree(tok->g_keys_dev);
     if (tok->g_child_dev) (void)hipFree(tok->g_child_dev);
     if (tok->g_token_dev) (void)hipFree(tok->g_token_dev);
+    if (tok->exp_tab_dev) (void)hipFree(tok->exp_tab_dev);
+    if (tok->exp_bytes_dev) (void)hipFree(tok->exp_bytes_dev);
     delete tok;
 }
 
@@ -368,6 +422,24 @@ extern "C" size_t ecgb_tokenizer_copy_runbits(const ecgb_tokenizer *tok, uint32_
     const size_t n = tok->runbits.size();
     if (out) std::memcpy(out, tok->runbits.data(), std::min(n, cap) * sizeof(uint32_t));
     return n;
+}
+
+extern "C" size_t ecgb_tokenizer_copy_expansions(const ecgb_tokenizer *tok, uint32_t *offsets_out, uint32_t *lens_out, size_t cap_ids,
+                                                 uint8_t *bytes_out, size_t cap_bytes)
+{
+    if (!tok || !tok->exp_built) return 0;
+    const size_t n_ids = tok->exp_tab.size() / 2;
+    for (size_t i = 0; i < std::min(n_ids, cap_ids); ++i) {
+        if (offsets_out) offsets_out[i] = tok->exp_tab[2 * i];
+        if (lens_out) lens_out[i] = tok->exp_tab[2 * i + 1];
+    }
+    if (bytes_out) std::memcpy(bytes_out, tok->exp_bytes.data(), std::min(tok->exp_bytes.size() - 16, cap_bytes));
+    return n_ids;
+}
+
+extern "C" size_t ecgb_tokenizer_expansion_bytes(const ecgb_tokenizer *tok)
+{
+    return (tok && tok->exp_built) ? tok->exp_bytes.size() - 16 : 0;
 }
 
 extern "C" int ecgb_tokenizer_info(const ecgb_tokenizer *tok, uint32_t *n_nodes, uint32_t *max_depth,

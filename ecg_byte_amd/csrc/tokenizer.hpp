@@ -36,6 +36,8 @@ inline uint64_t pack_node(uint32_t bitmap, uint32_t first_child, uint32_t token)
     return (uint64_t)bitmap | ((uint64_t)(first_child & 0xFFFFu) << 32) | ((uint64_t)(token & 0xFFFFu) << 48);
 }
 
+constexpr uint32_t kMaxExpansionIds = 1u << 22;   // ids the dense expansion table covers (32 MiB of offsets and lengths at the limit)
+
 void set_error(const std::string &msg);
 
 }  // namespace ecgb
@@ -68,6 +70,16 @@ struct ecgb_tokenizer {
     uint32_t *runbits_dev = nullptr;
     uint8_t *toklen_dev = nullptr;
     uint8_t *lut_dev = nullptr;        // 256 B byte_to_class | 64 B single_id | 32 B class_to_byte
+    // EXPANSION table (both forms; detokenize.hip): token id -> (offset into exp_bytes, length).  Ids 0..255 are their own byte, a merge id its expansion -- the LAST
+    // entry of the list that names the id, as a dict built in list order keeps it; length 0 = the id is not in the vocabulary (it occurs nowhere, its expansion is
+    // empty or holds an element above 255).  32-bit lengths: tok_len above cannot hold an expansion longer than 255.  Empty (exp_built false) when the largest id is
+    // kMaxExpansionIds or more: the table is dense, and the detokenise entry points then return ECGB_ERR_UNSUPPORTED.
+    std::vector<uint32_t> exp_tab;     // [2 * id] offset, [2 * id + 1] length
+    std::vector<uint8_t> exp_bytes;    // padded with 16 zero bytes
+    uint32_t exp_max_len = 0;
+    bool exp_built = false;
+    uint32_t *exp_tab_dev = nullptr;
+    uint8_t *exp_bytes_dev = nullptr;
     int device = -1;
     int n_cus = 0;                     // compute units of `device` (persistent grid size)
 };

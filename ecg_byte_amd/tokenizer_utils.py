@@ -1,15 +1,18 @@
 """Mirror of the reference's ecg_byte/utils/tokenizer_utils.py (same names, argument meaning and
-return shapes) with the compute on the MI355X.  Analysis/plot helpers of the reference
-(analyze_token_distribution, track_encoding) are out of scope.
+return shapes) with the compute on the MI355X.  The plot helper of the reference (track_encoding)
+is out of scope.  decode_batch / reconstruct_batch are the batched, on-device
+forms of decode_text / reverse_normalize_all (csrc/detokenize.hip).
 """
 from __future__ import annotations
 
 import pickle
+from collections import Counter
 
 import numpy as np
 import torch
 
 from . import rust_bpe
+from .tokenizer import HipTokenizer
 from .tokenizer import quantize as _quantize_dev
 
 ALPHABET = list("abcdefghijklmnopqrstuvwxyz")          # tokenizer_utils.py:12
@@ -108,3 +111,82 @@ def process_paths(paths, percentiles) -> bytes:
             flush()
     flush()
     return b"".join(parts)
+
+
+_BATCH = 256        # records per device batch (process_paths)
+
+
+def _tokenizer_of(merges) -> HipTokenizer:
+    return merges if isinstance(merges, HipTokenizer) else HipTokenizer(merges)
+
+
+def decode_batch(ids, counts, merges):
+    """decode_text for a batch, on the device: ids int32 `(B, stride)` and counts int32 `(B,)` (CUDA tensors or arrays, as
+    `HipTokenizer.quantize_encode` returns them) -> list of B `bytes`.  `merges` is the reference's list or a HipTokenizer.
+    Raises KeyError naming the first id that is not in the vocabulary, as `vocab[id]` would."""
+    tk = _tokenizer_of(merges)
+    ids = torch.as_tensor(np.asarray(ids) if not isinstance(ids, torch.Tensor) else ids).to(device="cuda", dtype=torch.int32)
+    counts = torch.as_tensor(np.asarray(counts) if not isinstance(counts, torch.Tensor) else counts).to(device="cuda", dtype=torch.int32)
+    if ids.dim() == 1:
+        ids = ids[None]
+    out, n_sym, flags = tk.detokenize(ids, counts)
+    flags = flags.cpu().numpy()
+    if (flags & 1).any():
+        lens = tk.expansions()[1]
+        b = int(np.flatnonzero(flags & 1)[0])
+        row = ids[b, : min(int(counts[b]), ids.shape[1])].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+        bad = row[(row >= lens.size) | (lens[np.minimum(row, lens.size - 1)] == 0)]
+        raise KeyError(int(bad[0]))
+    out, n_sym = out.cpu().numpy(), n_sym.cpu().numpy()
+    return [out[b, : n_sym[b]].tobytes() for b in range(out.shape[0])]
+
+
+def reconstruct_batch(signal, percentiles, merges):
+    """Quantise + encode -> detokenise back to signal, against the original, in one pass on the device: the self-check of
+    train_tokenizer.py:44-66 for a batch.  signal: `(B, 12, L)` or `(B, n)` float64 (numpy or CUDA tensor).  Returns a list of B
+    `(round_trip_ok, max_abs_diff, n_tokens)`: the decoded symbols are the quantised ones and all of them came back; the largest
+    |signal - dequantised| (what the reference prints); the record's token count."""
+    tk = _tokenizer_of(merges)
+    x = signal if isinstance(signal, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float64))
+    x = x.to(device="cuda", dtype=torch.float64).contiguous()
+    B = x.shape[0]
+    n = x.numel() // B if B else 0
+    if B == 0 or n == 0:
+        return [(True, 0.0, 0)] * B
+    ids, counts = tk.quantize_encode(x, percentiles)
+    _, n_sym, flags, diff, mism = tk.detokenize_signal(ids, counts, percentiles, n, original=x)
+    n_sym, flags, diff, mism, counts = (t.cpu().numpy() for t in (n_sym, flags, diff, mism, counts))
+    return [(bool(n_sym[b] == n and flags[b] == 0 and mism[b] == 0), float(diff[b]), int(counts[b])) for b in range(B)]
+
+
+def _record_batches(paths):
+    """Records of the listed .npy files as float64 batches of equal shape, in order (the batching of process_paths)."""
+    batch, shape = [], None
+    for p in paths:
+        sig = np.ascontiguousarray(np.load(p), dtype=np.float64)
+        if batch and (sig.shape != shape or len(batch) >= _BATCH):
+            yield np.stack(batch)
+            batch = []
+        shape = sig.shape
+        batch.append(sig)
+    if batch:
+        yield np.stack(batch)
+
+
+def analyze_token_distribution(test_data, merges, percentiles, num_workers=None):
+    """tokenizer_utils.py analyze_token_distribution: `(Counter of token ids over the test set, [token count of each record])`.
+    test_data: paths of (12, L) .npy records.  `num_workers` is accepted for compatibility; records are encoded on the GPU in
+    batches and counted there (ecgb_token_histogram_hip)."""
+    tk = _tokenizer_of(merges)
+    total, lengths = None, []
+    for x in _record_batches(list(test_data)):
+        ids, counts = tk.quantize_encode(torch.from_numpy(x).cuda(), percentiles)
+        hist, over = tk.token_histogram(ids, counts)
+        assert int(over) == 0, "the encoder emitted an id outside the tokenizer's id range"
+        total = hist if total is None else total + hist
+        lengths.extend(int(c) for c in counts.cpu().numpy())
+    token_counts = Counter()
+    if total is not None:
+        total = total.cpu().numpy()
+        token_counts.update({int(k): int(total[k]) for k in np.flatnonzero(total)})
+    return token_counts, lengths

@@ -6,8 +6,9 @@ Two stages, either of which can run alone:
   train       corpus string from the sampled .npy records (quantise on the device) -> `rust_bpe.byte_pair_encoding`
               (HIP trainer) -> pickle((vocab, merges))                                     [reference: 19-42]
   self-check  one record: quantise, encode with the stored merges, decode, compare         [reference: 44-66]
-`main` returns True when the decoded text equals the quantised text -- the reference prints that comparison; the tests
-use it.
+  --check_files F   after it, the same round trip over EVERY record listed in F, on the device (tokenizer_utils.reconstruct_batch)
+`main` returns True when the decoded text equals the quantised text (for every checked record) -- the reference prints that
+comparison; the tests use it.
 """
 from __future__ import annotations
 
@@ -29,6 +30,7 @@ _OPTIONS = (
     ("--train", "store_true", None, "train a tokenizer before the self-check"),
     ("--loaded", str, None, "existing tokenizer .pkl to check instead of the one just trained"),
     ("--check_ecg", str, "./data/seg_ecg_qa_ptb_500/ecg/train/ecg_10_1.npy", "record used by the self-check"),
+    ("--check_files", str, None, "text file of .npy paths: round-trip every listed record on the device after the one-record self-check"),
     ("--out", str, None, "where to write the tokenizer (default ./data/tokenizer_{num_merges}.pkl)"),
     ("--dis", "store_true", None, "started by torch.distributed.run, one process per GPU: every rank quantises its contiguous share of "
                                   "the listed records and trains on that slice of the corpus (RCCL; same merges as one GPU)"),
@@ -109,6 +111,29 @@ def self_check(tokenizer_path, record_path, percentiles) -> bool:
     return same
 
 
+def check_files(tokenizer_path, list_path, percentiles) -> bool:
+    """The round trip of `self_check` over every record listed in `list_path`, on the device; prints the totals."""
+    _, merges = tu.load_vocab_and_merges(tokenizer_path)
+    with open(list_path) as f:
+        paths = [line.strip() for line in f if line.strip()]
+    tk = tu.HipTokenizer(merges)
+    failed, symbols, tokens, worst, worst_path, done = 0, 0, 0, -1.0, None, 0
+    for x in tu._record_batches(paths):
+        for k, (ok, diff, n_tok) in enumerate(tu.reconstruct_batch(x, percentiles, tk)):
+            failed += not ok
+            symbols += x[k].size
+            tokens += n_tok
+            if diff != diff or diff > worst:          # a NaN difference is the worst there is, and stays
+                if worst == worst:
+                    worst, worst_path = diff, paths[done + k]
+        done += x.shape[0]
+    print(f"records checked: {done}")
+    print(f"round trips failed: {failed}")
+    print(f"total: {symbols} symbols -> {tokens} tokens ({symbols / max(1, tokens):.2f}x)")
+    print(f"largest |signal - dequantised| = {worst:.6g} in {worst_path}" if done else "largest |signal - dequantised|: no records")
+    return failed == 0
+
+
 def main(args) -> bool:
     percentiles = np.load(args.percentiles, allow_pickle=True).item()
     target = args.out or f"./data/tokenizer_{args.num_merges}.pkl"
@@ -128,7 +153,12 @@ def main(args) -> bool:
                 for line in report.lines():
                     print(line)
                 print(f"tokenizer written to {target}")
-        return self_check(args.loaded or target, args.check_ecg, percentiles) if rank == 0 else True
+        if rank != 0:
+            return True
+        ok = self_check(args.loaded or target, args.check_ecg, percentiles)
+        if args.check_files:
+            ok = check_files(args.loaded or target, args.check_files, percentiles) and ok
+        return ok
     finally:
         if args.dis:
             import torch.distributed as dist

@@ -22,6 +22,7 @@
  *   ecgb_assemble_hip          ECGTokenDataset._prepare_training / _prepare_inference,
  *                              ecg_byte/data_loader.py:91-132 (+ the id->LLM-id mapping of :80)
  *   ecgb_bpe_train_hip         rust_bpe.byte_pair_encoding, ecg_byte/rust_bpe/src/lib.rs:58-125
+ *   ecgb_detokenize_*_hip      decode_text / reverse_normalize_all, ecg_byte/utils/tokenizer_utils.py:75-77, 22-28
  * INTEGRATION.md shows the binding a reference maintainer would add for each.
  */
 #ifndef ECGBYTE_H
@@ -76,6 +77,16 @@ size_t ecgb_tokenizer_copy_nodes(const ecgb_tokenizer *tok, uint64_t *out, size_
  * with zero pairs) and returns the word count. */
 size_t ecgb_tokenizer_copy_runbits(const ecgb_tokenizer *tok, uint32_t *out, size_t cap);
 
+/* The expansion table of the handle (either trie form): token id -> (offset into one flat byte array, length).  Ids 0..255 expand to their own byte, an id of
+ * `merges` to its expansion -- the LAST entry of the list that names the id, as a dict built in list order keeps it.  Length 0 = the id is not in the vocabulary:
+ * it occurs nowhere, or its entry is empty or holds an element above 255.  Copies the first min(n_ids, cap_ids) offsets / lengths (either may be NULL) and the
+ * first min(n_bytes, cap_bytes) bytes and returns n_ids = largest id + 1; ecgb_tokenizer_expansion_bytes returns n_bytes.  A call with NULL pointers or zero
+ * capacities only returns the size.  The table is dense: a handle whose largest id is 2^22 or more has none (both return 0, and the detokenise entry points
+ * ECGB_ERR_UNSUPPORTED).  Works on a host-only handle. */
+size_t ecgb_tokenizer_copy_expansions(const ecgb_tokenizer *tok, uint32_t *offsets_out, uint32_t *lens_out, size_t cap_ids, uint8_t *bytes_out,
+                                      size_t cap_bytes);
+size_t ecgb_tokenizer_expansion_bytes(const ecgb_tokenizer *tok);
+
 /* ---- quantiser --------------------------------------------------------------------------
  * normalize_all for n float64 samples: sym_dev[i] = alphabet index 0..25 ('a'+index is the
  * reference's character).  If clipped_dev != NULL it also receives the reference's first
@@ -124,6 +135,38 @@ int ecgb_quantize_encode_hip(const ecgb_tokenizer *tok, const double *signal_dev
                              size_t n_per_record, double percentile_1, double percentile_99,
                              uint32_t *ids_dev, size_t ids_stride, uint32_t *counts_dev,
                              void *scratch_dev, size_t scratch_bytes, void *stream);
+
+/* ---- detokenise: token ids back to symbols, per-symbol values and signal (detokenize.hip) -------------------------------
+ * The inverse of the encoder: tokenizer_utils.py:75-77 decode_text, :22-28 reverse_normalize_all, the interpret run's expand_attention and the Counter of
+ * analyze_token_distribution, for a batch.  ("decode" names the LLM's decode step in this library, hence the name.)
+ * ids_dev / ids_stride / counts_dev / batch: encoder output as ecgb_*encode_hip write it; record b's tokens are ids_dev[b * ids_stride .. + min(counts[b],
+ * ids_stride)); entries past that are never read as ids.  Every output row has out_stride ELEMENTS; rows need no alignment beyond their element's.
+ * n_sym_dev[b] = symbols produced, flags_dev[b] = bits, per record (one record's trouble never touches another's row):
+ *   bit 0  an id without an expansion was met: it contributes nothing and the record goes on
+ *   bit 1  the expansion is longer than out_stride: the row is cut there, n_sym = out_stride, nothing is written past the row
+ *   bit 2  (signal form) a decoded byte outside 'a'..'z': that position receives NaN
+ * Positions n_sym[b] .. out_stride of a row are left as they were.  Limits: expansions of at most 2^20 bytes, id rows shorter than 2^31 and output rows shorter than 2^32, token ids below 2^22.
+ *   ecgb_detokenize_hip             out[b] = the concatenated expansions (bytes)
+ *   ecgb_detokenize_values_f32_hip  out[b][p] = values_dev[b * ids_stride + t] for the token t that covers position p (moved as bits)
+ *   ecgb_detokenize_signal_f64_hip  out[b][p] = ((byte - 'a') / 25.0) * (max - min) + min, min = percentile_1 - 0.5, max = percentile_99 + 0.5, one IEEE
+ *                                   operation at a time: the bits numpy gives.  With original_dev != NULL (rows of original_stride doubles) also, over the
+ *                                   produced positions below original_stride: max_abs_diff_dev[b] = max |original - out| (NaN if any difference is NaN, as
+ *                                   np.max; 0 for an empty record) and n_mismatch_dev[b] = positions where the quantiser's level of `original` (the bin edges
+ *                                   of ecgb_quantize_hip) is not the decoded symbol.
+ *   ecgb_token_histogram_hip        hist_dev[k] = occurrences of id k over every record's valid tokens, k < n_bins; *overflow_dev = ids >= n_bins.  Both are
+ *                                   zeroed on the stream first.  Integer atomics: the same bits every run.
+ *   ecgb_detokenize_tile            the kernel's blocking: tokens scanned per chunk, output positions per tile (for tests that place edge cases). */
+int ecgb_detokenize_hip(const ecgb_tokenizer *tok, const uint32_t *ids_dev, size_t ids_stride, const uint32_t *counts_dev, size_t batch,
+                        uint8_t *out_dev, size_t out_stride, uint32_t *n_sym_dev, uint32_t *flags_dev, void *stream);
+int ecgb_detokenize_values_f32_hip(const ecgb_tokenizer *tok, const uint32_t *ids_dev, size_t ids_stride, const uint32_t *counts_dev, size_t batch,
+                                   const float *values_dev, float *out_dev, size_t out_stride, uint32_t *n_sym_dev, uint32_t *flags_dev, void *stream);
+int ecgb_detokenize_signal_f64_hip(const ecgb_tokenizer *tok, const uint32_t *ids_dev, size_t ids_stride, const uint32_t *counts_dev, size_t batch,
+                                   double percentile_1, double percentile_99, double *out_dev, size_t out_stride, uint32_t *n_sym_dev,
+                                   uint32_t *flags_dev, const double *original_dev, size_t original_stride, double *max_abs_diff_dev,
+                                   uint32_t *n_mismatch_dev, void *stream);
+int ecgb_token_histogram_hip(const uint32_t *ids_dev, size_t ids_stride, const uint32_t *counts_dev, size_t batch, uint64_t *hist_dev, size_t n_bins,
+                             uint64_t *overflow_dev, void *stream);
+void ecgb_detokenize_tile(uint32_t *tokens_per_chunk, uint32_t *symbols_per_tile);
 
 /* ---- sequence assembly -------------------------------------------------------------------
  * ECGTokenDataset._prepare_training (inference == 0, data_loader.py:101-132) or
