@@ -227,6 +227,8 @@ def lib():
         "ecgb_gemm_nn_splitk_bf16": [vp, ll, vp, ll, vp, vp, ci, ci, ci, ci, f32, vp],
         "ecgb_gemm_nt_glu_bf16": [vp, ll, vp, ll, vp, ll, vp, ll, ci, vp, ll, vp, ll, ci, ci, ci, f32, ci, vp],
         "ecgb_gemm_nt_bf16_cat": [vp, ll, vp, ll, vp, ll, vp, ll, ci, vp, ll, ci, ci, ci, f32, ci, vp],
+        "ecgb_gemm_nt_rows_bf16": [vp, ll, vp, ll, vp, ll, vp, ll, ci, vp, ll, ci, ci, ci, f32, vp, sz, vp],
+        "ecgb_gemm_nt_rows_glu_bf16": [vp, ll, vp, ll, vp, ll, vp, ll, ci, vp, ll, ci, ci, ci, f32, ci, vp, sz, vp],
         "ecgb_layernorm_fwd": [vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, f32, vp],
         "ecgb_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, vp, vp],
         "ecgb_bias_act": [vp, vp, vp, sz, ci, ci, vp],
@@ -248,6 +250,8 @@ def lib():
     for name in ("ecgb_layernorm_bwd_scratch_floats", "ecgb_colsum_scratch_floats"):
         getattr(L, name).argtypes = [sz, ci]
         getattr(L, name).restype = sz
+    L.ecgb_gemm_nt_rows_scratch_bytes.argtypes = [ci, ci, ci]
+    L.ecgb_gemm_nt_rows_scratch_bytes.restype = sz
     L.ecgb_sample_scratch_bytes.argtypes = [ci]
     L.ecgb_sample_scratch_bytes.restype = sz
     L.ecgb_partial_rows_sum_f32.argtypes = [vp, ci, ci, ll, vp, vp]

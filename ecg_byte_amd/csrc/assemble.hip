@@ -55,6 +55,10 @@ __global__ __launch_bounds__(256) void assemble_kernel(AssembleArgs A)
         n_used = avail; npad = 0; len = 2 + n_used + 1 + nq;
         if (len > A.row_len) { n_used -= min(n_used, len - A.row_len); len = 2 + n_used + 1 + nq; }
         if (tid == 0) A.lengths[b] = len;
+        if (A.inference == 2) {   // a batch of prompts: the same prompt right-aligned in the row, pad ids and mask 0 in front (what generate() expects of a batch)
+            npad = len < A.row_len ? A.row_len - len : 0u;
+            len = A.row_len;
+        }
     } else {
         const uint32_t space = A.pad_to_max - nq - na;   // host guarantees nq + na <= pad_to_max
         n_used = min(avail, space);

@@ -50,7 +50,9 @@ class BatchAssembler:
     def assemble(self, ids, counts, questions, answers=None, inference=False):
         """ids/counts: encoder output.  questions/answers: per-sample lists of LLM ids.
         Training -> dict of `[B, pad_to_max+4]` device tensors with the reference's keys
-        (data_loader.py:126-131); inference -> `tokenized_signal`, `attn_mask`, `lengths`."""
+        (data_loader.py:126-131); inference -> `tokenized_signal`, `attn_mask`, `lengths`: one prompt as the reference
+        builds it (padded behind, `lengths` says where it ends); several prompts right-aligned with pad ids and mask 0
+        in front -- the batch a left-padded generate() takes -- and trimmed so that the longest prompt has no pad."""
         B = ids.shape[0]
         q_flat, q_off, q_len = _as_i32_concat(questions, self.device)
         if inference:
@@ -77,9 +79,12 @@ class BatchAssembler:
             _ptr(ids), ids.shape[1], _ptr(counts), B, _ptr(self.lut), self.lut.numel(),
             _ptr(q_flat), _ptr(q_off), _ptr(a_flat), _ptr(a_off),
             self.pad_id, self.bos_id, self.eos_id, self.sig_start_id, self.sig_end_id,
-            self.pad_to_max, 1 if inference else 0, row_len,
+            self.pad_to_max, (2 if B > 1 else 1) if inference else 0, row_len,
             _ptr(input_ids), _ptr(attn), _ptr(labels), _ptr(pos), _ptr(lengths), _stream_ptr()))
         if inference:
+            if B > 1:
+                cut = row_len - int(lengths.max().item())
+                input_ids, attn = input_ids[:, cut:], attn[:, cut:]
             return {"tokenized_signal": input_ids, "attn_mask": attn, "lengths": lengths}
         return {"tokenized_signal": input_ids, "attn_mask": attn,
                 "quantized_signal_ids_input": labels, "position_ids": pos}
@@ -178,7 +183,8 @@ class DeviceBatchLoader:
     Here a thread pool reads and tokenizes the next batches while the current one trains; a batch's signals are
     stacked in pinned host memory, copied on a side stream, and quantise -> encode -> assemble run once per batch on
     the device.  Yields the reference's batch dict with device tensors (training: tokenized_signal, attn_mask,
-    quantized_signal_ids_input, position_ids; inference, batch size 1: answer, question, tokenized_signal, attn_mask).
+    quantized_signal_ids_input, position_ids; inference: answer, question (lists), tokenized_signal, attn_mask [B, S] --
+    batch size 1 the reference's single prompt, larger batches left-padded to their longest prompt).
     Samples that fail to load are dropped from their batch; a batch with no valid sample is yielded as None, which
     the runners skip (train.py:17-19)."""
 
@@ -188,8 +194,6 @@ class DeviceBatchLoader:
         self.drop_last, self.seed, self.workers, self.prefetch = drop_last, seed, max(1, workers), max(1, prefetch)
         self.epoch = 0
         self.stall_s, self.batches_out = 0.0, 0       # host seconds the consumer spent waiting for a batch the readers had not finished; batches yielded
-        if bool(dataset.args.inference) and self.batch_size != 1:
-            raise ValueError("inference batches are single prompts (main.py:181-184 uses batch_size=1)")
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else len(self.dataset)
@@ -266,6 +270,9 @@ class DeviceBatchLoader:
                 if inference:
                     ids, counts = ds.assembler.encode(dev, ds.percentiles)
                     r = ds.assembler.assemble(ids, counts, q, inference=True)
+                    if len(q) > 1:                            # left-padded and trimmed by the assembler (its one read of the lengths)
+                        yield {"answer": ans, "question": qs, "tokenized_signal": r["tokenized_signal"], "attn_mask": r["attn_mask"]}
+                        continue
                     n = int(r["lengths"][0].item())
                     yield {"answer": ans, "question": qs, "tokenized_signal": r["tokenized_signal"][:, :n],
                            "attn_mask": r["attn_mask"][:, :n]}

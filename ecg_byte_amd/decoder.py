@@ -137,12 +137,22 @@ class LoraSite(nn.Module):
         lo = 16 * self.spb * b
         return lo, lo + self.r
 
-    def project(self, x, w, training, keep=False, glu=None, rope=None, t_pre=None, sync=None):
+    def project(self, x, w, training, keep=False, glu=None, rope=None, t_pre=None, sync=None, rows=False):
         """y = x W^T + the adapter branch, [T, out].  Returns (y, what backward needs).
         glu = (gelu_tanh, keep_gu): the site is the fused gate|up projection and the GLU runs in the GEMM's epilogue; y is then the pair
         (gate|up or None, act(gate) * up).  sync: the model's decode-step counter (int32[1], a new value every step) -- a decode step's o / down site then forms t and the
-        projection in ONE launch (ops.gemm_nt_lora_decode: the same bits)."""
+        projection in ONE launch (ops.gemm_nt_lora_decode: the same bits).  rows: a batched decode step (9..64 rows, HipCausalLM.decode_rows) -- t, the projection
+        and the GLU go to the weight-streaming kernels (ops.gemm_nt_rows / gemm_nt_rows_glu) wherever ops.gemm_nt_rows_ok takes the shape."""
         p, seed = 0.0, 0
+        if rows and not training and rope is None:
+            M, K = x.shape
+            t = t_pre
+            if t is None and ops.gemm_nt_rows_ok(M, self.A.shape[0], K, strides=(x.stride(0),)):
+                t = ops.gemm_nt_rows(x, self.A.data, alpha=self.scale)
+            if t is not None and ops.gemm_nt_rows_ok(M, w.shape[0], K, t.shape[1], strides=(x.stride(0), t.stride(0))):
+                if glu is not None:
+                    return (None, ops.gemm_nt_rows_glu(x, w, gelu_tanh=glu[0], a2=t, b2=self.B.data)), None
+                return ops.gemm_nt_rows(x, w, a2=t, b2=self.B.data), None
         if training and self.p > 0:
             # One mask stream per (site, rank, call): data-parallel ranks draw DIFFERENT masks (torch's per-process generators give the
             # reference's DDP ranks different dropout too); `calls` restarts at 0 with a new process -- the reference never resumes
@@ -262,6 +272,7 @@ class HipCausalLM(nn.Module):
     # own forward / backward do not (HipGPT2LM) sets this False and gets the plain in-stream step
     supports_optimizer_overlap = True
     output_attentions_built = True   # forward(output_attentions=...) served by _hidden_states(attn_out=...); a subclass with its own _hidden_states sets False
+    decode_rows = True          # a decode step of 9..64 sequences runs its projections and the head on the weight-streaming kernels (ops.gemm_nt_rows); False: the tile kernels
     decode_attn_one = True      # a decode step's RoPE + append + attention as one launch where the shape allows (ops.decode_one_ok); False: round 4's four launches, the same bits
     decode_lora_one = False     # True: a decode step's o / down adapter sites form t = scale * x A^T inside the projection's launch (ops.gemm_nt_lora_decode: two launches a layer less, the same
                                 # bits) -- measured 503 against 508 tokens/s at the C5 shape: two dependent dot products and a hand-over between XCDs take what the launch boundary took
@@ -586,23 +597,37 @@ class HipCausalLM(nn.Module):
             return ops.gemm_nn_splitk(dy, p.data, splits)
         return ops.gemm_nt(dy, self._shadow(key, p))
 
-    def _proj(self, i, key, x, w, training=False, keep=False, rope=None, t_pre=None, sync=None):
+    def _rows_route(self, B):
+        """Does a decode step of B sequences take the 9..64-row kernels (each site still asks ops.gemm_nt_rows_ok for its own shape)?"""
+        return bool(self.decode_rows) and not self.training and 8 < B <= 64
+
+    def _head_rows(self, last, rows):
+        """The tied head behind a decode step: logits [B, padded vocabulary]."""
+        if rows and ops.gemm_nt_rows_ok(last.shape[0], self.embed.shape[0], last.shape[1], strides=(last.stride(0),)):
+            return ops.gemm_nt_rows(last, self.embed.data)
+        return ops.gemm_nt(last, self.embed.data)
+
+    def _proj(self, i, key, x, w, training=False, keep=False, rope=None, t_pre=None, sync=None, rows=False):
         """One projection of layer i ("qkv", "o", "gu", "down"): x W^T, plus the LoRA branch of the site when adapters are on
         (in the same launch).  rope = (cos, sin, columns): the q|k|v projection leaves with its q and k heads rotated (apply_rotary_pos_emb in the GEMM's
         epilogue where the kernel takes the shape, else as the separate pass).  Returns (y, what the adapter's backward needs or None)."""
         if self.lora is None:
             if rope is not None:
                 return ops.gemm_nt_rope(x, w, rope[0], rope[1], rope[2]), None
+            if rows and ops.gemm_nt_rows_ok(x.shape[0], w.shape[0], x.shape[1], strides=(x.stride(0),)):
+                return ops.gemm_nt_rows(x, w), None
             return ops.gemm_nt(x, w), None
-        return self.lora[i][key].project(x, w, training, keep, rope=rope, t_pre=t_pre, sync=sync)
+        return self.lora[i][key].project(x, w, training, keep, rope=rope, t_pre=t_pre, sync=sync, rows=rows)
 
-    def _proj_glu(self, i, x, training=False, keep=False, keep_gu=True, t_pre=None):
+    def _proj_glu(self, i, x, training=False, keep=False, keep_gu=True, t_pre=None, rows=False):
         """The MLP's gate|up projection with the GLU in the GEMM's epilogue: returns (gate|up [T, 2I] or None, act(gate) * up [T, I],
         adapter state).  gate|up is what the backward needs; inference passes keep_gu=False and the tensor is never written."""
         w = self.wgu[i].data
         if self.lora is not None:
-            (gu, hm), ls = self.lora[i]["gu"].project(x, w, training, keep, glu=(self.gemma, keep_gu), t_pre=t_pre)
+            (gu, hm), ls = self.lora[i]["gu"].project(x, w, training, keep, glu=(self.gemma, keep_gu), t_pre=t_pre, rows=rows and not keep_gu)
             return gu, hm, ls
+        if rows and not keep_gu and ops.gemm_nt_rows_ok(x.shape[0], w.shape[0], x.shape[1], strides=(x.stride(0),)):
+            return None, ops.gemm_nt_rows_glu(x, w, gelu_tanh=self.gemma), None
         if ops.glu_fusable(x.shape[0], w.shape[0] // 2):
             gu, hm = ops.gemm_nt_glu(x, w, gelu_tanh=self.gemma, keep_gu=keep_gu)
         else:
@@ -610,14 +635,14 @@ class HipCausalLM(nn.Module):
             hm = ops.glu_fwd(gu, gelu_tanh=self.gemma)
         return gu, hm, None
 
-    def _norm(self, i, key, x, delta, with_t=False):
+    def _norm(self, i, key, x, delta, with_t=False, rows=False):
         """The RMSNorm in front of layer i's "qkv" or "gu" projection over x (+ delta): returns (h, x + delta, t).  t = scale * h A^T of that site's adapters, formed by
         the norm kernel on its way out (one launch less, the same bits), when the caller asks for it (with_t), adapters are on and the model is in eval mode; else None
         (training mode, also under torch.no_grad(): the site forms its own t, with its dropout)."""
         w = (self.ln1 if key == "qkv" else self.ln2)[i].data
         if with_t and self.lora is not None and not self.training:
             site = self.lora[i][key]
-            h, _, x, t = ops.rmsnorm_fwd(x, w, self.cfg.rms_norm_eps, residual=delta, gemma=self.gemma, lora=(site.A.data, site.scale))
+            h, _, x, t = ops.rmsnorm_fwd(x, w, self.cfg.rms_norm_eps, residual=delta, gemma=self.gemma, lora=(site.A.data, site.scale), rows=rows)
             return h, x, t
         h, _, x = ops.rmsnorm_fwd(x, w, self.cfg.rms_norm_eps, residual=delta, gemma=self.gemma)
         return h, x, None
@@ -978,16 +1003,18 @@ class HipCausalLM(nn.Module):
             hf = hf.view(B, S, -1)[:, lpad:].reshape(B * (S - lpad), -1)
         return hf
 
-    def _layer_infer(self, i, x, delta, attend, rope=None, norm_t=(), sync=None):
+    def _layer_infer(self, i, x, delta, attend, rope=None, norm_t=(), sync=None, rows=False):
         """Layer i without anything kept for a backward: (x, delta) -> (x + delta + the attention's share, the MLP's share).  attend(i, qkv) is the caller's attention:
         a whole batch (_hidden_states, with rope: the q|k|v projection rotates q and k) or one new token against the caches (_decode_step: RoPE inside the attention).
-        norm_t: the adapter sites among "qkv", "gu" whose t the norm in front of them forms (see _norm); sync: LoraSite.project's, for the o and down sites."""
-        h1, x, t1 = self._norm(i, "qkv", x, delta, "qkv" in norm_t)
-        qkv, _ = self._proj(i, "qkv", h1, self.wqkv[i].data, rope=rope, t_pre=t1)
-        attn_delta, _ = self._proj(i, "o", attend(i, qkv), self.wo[i].data, sync=sync)
-        h2, x, t2 = self._norm(i, "gu", x, attn_delta, "gu" in norm_t)
-        _, hm, _ = self._proj_glu(i, h2, keep_gu=False, t_pre=t2)
-        return x, self._proj(i, "down", hm, self.wdown[i].data, sync=sync)[0]
+        norm_t: the adapter sites among "qkv", "gu" whose t the norm in front of them forms (see _norm); sync: LoraSite.project's, for the o and down sites;
+        rows: a batched decode step (_rows_route) -- every product of the layer may take the 9..64-row kernels.  _hidden_states never passes it: a short prefill of as many
+        rows keeps its kernels and its bits."""
+        h1, x, t1 = self._norm(i, "qkv", x, delta, "qkv" in norm_t, rows=rows)
+        qkv, _ = self._proj(i, "qkv", h1, self.wqkv[i].data, rope=rope, t_pre=t1, rows=rows)
+        attn_delta, _ = self._proj(i, "o", attend(i, qkv), self.wo[i].data, sync=sync, rows=rows)
+        h2, x, t2 = self._norm(i, "gu", x, attn_delta, "gu" in norm_t, rows=rows)
+        _, hm, _ = self._proj_glu(i, h2, keep_gu=False, t_pre=t2, rows=rows)
+        return x, self._proj(i, "down", hm, self.wdown[i].data, sync=sync, rows=rows)[0]
 
     def _eval_loss(self, input_ids, attention_mask, labels, position_ids, attn_out=None):
         """ForCausalLMLoss (loss_utils.py:24-47) without a backward: forward-only hidden states, lm_head + cross entropy
@@ -1023,6 +1050,7 @@ class HipCausalLM(nn.Module):
             if not epoch_advanced:
                 sync.add_(1)
         nn = n if n_dev is None else n_dev
+        rows = self._rows_route(x.shape[0])
         if self.decode_fused and not self.training and ops.decode_fusable(x.shape[0], c.hidden_size, c.num_attention_heads, c.num_key_value_heads, c.head_dim):
             return self._decode_layers_fused(x, cos, sin, mask, caches, nn)
 
@@ -1030,7 +1058,7 @@ class HipCausalLM(nn.Module):
             return self._decode_attend(qkv, cos, sin, caches[i], mask, nn, scratch, scratch_one, one=self.decode_attn_one)
 
         for i in range(c.num_hidden_layers):
-            x, delta = self._layer_infer(i, x, delta, attend, norm_t=("qkv", "gu"), sync=sync)     # adapters: both norms form their site's t (_hidden_states: gate|up only)
+            x, delta = self._layer_infer(i, x, delta, attend, norm_t=("qkv", "gu"), sync=sync, rows=rows)     # adapters: both norms form their site's t (_hidden_states: gate|up only)
         hf, _, _ = ops.rmsnorm_fwd(x, self.norm.data, c.rms_norm_eps, residual=delta, gemma=self.gemma)
         return hf
 
@@ -1251,7 +1279,7 @@ class HipCausalLM(nn.Module):
             else:
                 pos = positions(mask[:, :n])[:, -1]
                 last = self._decode_step(seq[:, -1].contiguous(), pos, mask, caches, n)
-            logits = ops.gemm_nt(last, self.embed.data)
+            logits = self._head_rows(last, rows=t > 0 and use_cache and self._rows_route(B))      # (the prefill's head keeps its kernel, as in _generate_graph)
             if return_logits:
                 step_logits.append(logits[:, :c.vocab_size].float())
             nxt = pick(logits, n)
@@ -1298,7 +1326,7 @@ class HipCausalLM(nn.Module):
         cap = -(-(S0 + max_new_tokens) // 128) * 128
         pad_id = pad_token_id if pad_token_id is not None else 0
         key = (B, cap, pad_id, None if eos is None else tuple(int(e) for e in eos.tolist()), sampling, self.training, self.embed.data_ptr(),
-               None if self.lora is None else self.lora[0]["qkv"].A.data_ptr(), self.wqkv[0].data_ptr(), bool(self.decode_attn_one), bool(self.decode_lora_one))      # (the last: base weights or their merged copies)
+               None if self.lora is None else self.lora[0]["qkv"].A.data_ptr(), self.wqkv[0].data_ptr(), bool(self.decode_attn_one), bool(self.decode_lora_one), bool(self.decode_rows))      # (the weights: base weights or their merged copies)
         if device_sampler:
             key = key + (True,)
         reuse = sampling is None or device_sampler                           # (torch's sampling step holds its sort / cumsum / multinomial: captured per call)
@@ -1362,7 +1390,7 @@ class HipCausalLM(nn.Module):
         def step():
             one = self.lora is not None and not self.training and self.decode_lora_one
             last = self._decode_step(tok, pos, gmask, caches, None, n_dev, scratch=st.scratch, scratch_one=st.scratch_one, epoch_advanced=one)
-            nx = pick(ops.gemm_nt(last, self.embed.data), n_dev)      # (n_dev: the tokens present, as `n` in the eager loop)
+            nx = pick(self._head_rows(last, rows=self._rows_route(B)), n_dev)      # (n_dev: the tokens present, as `n` in the eager loop)
             # pad for finished sequences, the eos test, the token into `out` and `tok`, the mask's new column, the three counters: one launch (six to eleven
             # element-wise ones before, 5 us each in the replayed graph)
             ops.decode_advance_(nx.to(torch.int64), tok, pos, col, n_dev, out, gmask, unfinished, pad_id, eos_i64, epoch=self._decode_epoch(dev) if one else None)

@@ -212,12 +212,12 @@ def embed_bwd(ids, dout, grad_table_f32, scale=1.0):
     _lib.check(_L().ecgb_embed_bwd(_p(ids.contiguous()), _p(_bf(dout)), _p(grad_table_f32), ids.numel(), dout.shape[-1], float(scale), _st()))
 
 
-def rmsnorm_fwd(x, w, eps, residual=None, gemma=False, lora=None):
+def rmsnorm_fwd(x, w, eps, residual=None, gemma=False, lora=None, rows=False):
     """Returns (y, rstd, x_sum): x_sum = x + residual when residual is given (else x itself).
     lora = (A [n, H] bf16, scale), up to eight rows (a decode step with adapters): also returns t = gemm_nt(y, A, alpha=scale) as a fourth value, computed in the
-    same launch (ecgb_rmsnorm_lora_fwd; the same bits as the few-row GEMM)."""
+    same launch (ecgb_rmsnorm_lora_fwd; the same bits as the few-row GEMM).  rows: a batched decode step -- t of 9..64 rows comes from gemm_nt_rows."""
     H = x.shape[-1]
-    rows = x.numel() // H
+    rows_kernel, rows = rows, x.numel() // H
     y = torch.empty_like(x)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
     s = torch.empty_like(x) if residual is not None else None
@@ -229,7 +229,8 @@ def rmsnorm_fwd(x, w, eps, residual=None, gemma=False, lora=None):
                                                   _p(A), A.stride(0), A.shape[0], float(scale), _p(t), t.stride(0), _st()))
             return y, rstd, (s if residual is not None else x), t
         _lib.check(_L().ecgb_rmsnorm_fwd(_p(_bf(x)), _p(residual), _p(_bf(w)), _p(y), _p(s), _p(rstd), rows, H, float(eps), int(gemma), _st()))
-        return y, rstd, (s if residual is not None else x), gemm_nt(y.view(rows, H), A, alpha=scale)
+        gemm = gemm_nt_rows if rows_kernel and gemm_nt_rows_ok(rows, A.shape[0], H, strides=(A.stride(0),)) else gemm_nt
+        return y, rstd, (s if residual is not None else x), gemm(y.view(rows, H), A, alpha=scale)
     _lib.check(_L().ecgb_rmsnorm_fwd(_p(_bf(x)), _p(residual), _p(_bf(w)), _p(y), _p(s), _p(rstd), rows, H, float(eps), int(gemma), _st()))
     return y, rstd, (s if residual is not None else x)
 
@@ -505,6 +506,62 @@ def gemm_nt_glu(a, b, gelu_tanh=False, keep_gu=True, a2=None, b2=None, alpha=1.0
                                           b2.stride(0) if K2 else 0, K2, _p(gu), 2 * inter, _p(h), inter, M, inter, K, float(alpha),
                                           int(gelu_tanh), _st()))
     return gu, h
+
+
+rows_calls = 0        # launches of the 9..64-row kernels (gemm_nt_rows, gemm_nt_rows_glu): tests assert that a batched decode step ran them
+
+
+def gemm_nt_rows_ok(M, N, K, K2=0, strides=(), ptrs=()):
+    """Does ecgb_gemm_nt_rows_bf16 / _glu take this product?  Pure arithmetic, the rule of the C check (rows_domain and the alignment test in csrc/gemm_rows.hip):
+    8 < M <= 64, K and K2 multiples of 64, any N; strides: the operands' row strides (% 8), ptrs: their addresses (% 16)."""
+    return (8 < M <= 64 and N >= 1 and K >= 64 and K % 64 == 0 and K2 >= 0 and K2 % 64 == 0
+            and all(s % 8 == 0 for s in strides) and all(p % 16 == 0 for p in ptrs))
+
+
+def _rows_scratch(M, N, K, device):
+    # a fresh buffer per call: the call fills every slab it reads, and a captured graph keeps the buffer of its own capture alive
+    need = _L().ecgb_gemm_nt_rows_scratch_bytes(M, N, K)
+    return (torch.empty(need, dtype=torch.uint8, device=device), need) if need else (None, 0)
+
+
+def gemm_nt_rows(a, b, a2=None, b2=None, alpha=1.0, out=None):
+    """gemm_nt for 9..64 rows (a batched decode step): C[M,N] = alpha * (A B^T [+ A2 B2^T]) on the weight-streaming kernel (ecgb_gemm_nt_rows_bf16).
+    a may be a column-slice view; out: bf16 [>= M, >= N] with unit column stride, rows M.. and columns N.. are left alone."""
+    global rows_calls
+    M, K = a.shape
+    N = b.shape[0]
+    assert b.shape[1] == K and a.stride(1) == 1 and b.stride(1) == 1
+    K2 = 0
+    if a2 is not None:
+        K2 = a2.shape[1]
+        assert a2.shape[0] == M and b2.shape == (N, K2) and a2.stride(1) == 1 and b2.stride(1) == 1
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    assert out.dtype == torch.bfloat16 and out.stride(1) == 1 and out.shape[0] >= M and out.shape[1] >= N
+    buf, need = _rows_scratch(M, N, K, a.device)
+    _lib.check(_L().ecgb_gemm_nt_rows_bf16(_p(a), a.stride(0), _p(b), b.stride(0), _p(a2), a2.stride(0) if K2 else 0, _p(b2), b2.stride(0) if K2 else 0, K2,
+                                           _p(out), out.stride(0), M, N, K, float(alpha), _p(buf), need, _st()))
+    rows_calls += 1
+    return out
+
+
+def gemm_nt_rows_glu(a, b, gelu_tanh=False, a2=None, b2=None):
+    """h [M, I] = act(gate) * up of gate|up = A B^T [+ A2 B2^T], B = [2I, K] (gate rows, then up rows), for 9..64 rows (ecgb_gemm_nt_rows_glu_bf16): the bits of
+    glu_fwd(gemm_nt_rows(a, b, a2, b2)), gate|up never written."""
+    global rows_calls
+    M, K = a.shape
+    inter = b.shape[0] // 2
+    assert b.shape == (2 * inter, K) and a.stride(1) == 1 and b.stride(1) == 1
+    K2 = 0
+    if a2 is not None:
+        K2 = a2.shape[1]
+        assert a2.shape[0] == M and b2.shape == (2 * inter, K2) and a2.stride(1) == 1 and b2.stride(1) == 1
+    h = torch.empty((M, inter), dtype=torch.bfloat16, device=a.device)
+    buf, need = _rows_scratch(M, 2 * inter, K, a.device)
+    _lib.check(_L().ecgb_gemm_nt_rows_glu_bf16(_p(a), a.stride(0), _p(b), b.stride(0), _p(a2), a2.stride(0) if K2 else 0, _p(b2), b2.stride(0) if K2 else 0, K2,
+                                               _p(h), inter, M, inter, K, 1.0, int(gelu_tanh), _p(buf), need, _st()))
+    rows_calls += 1
+    return h
 
 
 def dropout(x, p, seed, out=None):

@@ -30,6 +30,16 @@ class LLM(nn.Module):
         return tokenizer.batch_decode(generated_ids[:, input_len:], skip_special_tokens=True,
                                       clean_up_tokenization_spaces=False)[0]
 
+    def generate_batch(self, batch, tokenizer):
+        """`generate` for a left-padded batch of prompts (data_loader.DeviceBatchLoader with batch_size > 1): the same call, every row decoded."""
+        dev = self.llm.device
+        input_len = batch["tokenized_signal"].shape[1]
+        generated_ids = self.llm.generate(input_ids=batch["tokenized_signal"].to(dev), attention_mask=batch["attn_mask"].to(dev),
+                                          max_new_tokens=128, pad_token_id=tokenizer.pad_token_id,
+                                          eos_token_id=tokenizer.eos_token_id, use_cache=True,
+                                          device_sampler=getattr(self.args, "device_sampler", None))
+        return list(tokenizer.batch_decode(generated_ids[:, input_len:], skip_special_tokens=True, clean_up_tokenization_spaces=False))
+
     # checkpoints are `{'model': model.state_dict(), 'epoch': epoch}` with this module's prefix (main.py:299-306)
     def state_dict(self, *a, **k):
         return {"llm." + n: t for n, t in self.llm.state_dict().items()}

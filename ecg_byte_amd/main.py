@@ -63,6 +63,10 @@ def get_args(argv=None):
     p.add_argument("--data_root", type=str, default="./data")
     p.add_argument("--runs_root", type=str, default="./runs")
     p.add_argument("--workers", type=int, default=4, help="reader threads of the batch loader")
+    p.add_argument("--inference_batch", type=int, default=1,
+                   help="--inference: prompts generated per step (1 = the reference's loop; up to 64 run a decode step on the 9..64-row kernels).  Samples are still scored "
+                        "one by one.  With a sampling checkpoint and --device_sampler a row's random stream is keyed by its row index, so batched draws differ from "
+                        "batch-1 draws at the same seed (the distribution is the same)")
     p.add_argument("--device_sampler", action="store_true",
                    help="inference with a sampling checkpoint: draw the token on the device inside the replayed decode step (HipCausalLM.generate(device_sampler=True))")
     return p.parse_args(argv)
@@ -111,7 +115,7 @@ def _inference(args, model, tokenizer, vocab, merges, data, device):
         np.random.seed(seed)
         checkpoint = torch.load(f"{ckpt_dir}/best_model.pth", map_location=device)
         model.load_state_dict(checkpoint["model"])
-        seed_results = tester(model, DeviceBatchLoader(test_data, batch_size=1, workers=args.workers), tokenizer, args)
+        seed_results = tester(model, DeviceBatchLoader(test_data, batch_size=max(1, int(getattr(args, "inference_batch", 1))), workers=args.workers), tokenizer, args)
         all_seed_results.append(seed_results)
         with open(f"{ckpt_dir}/seed_{seed}_results_{args.dataset}.json", "w") as f:
             json.dump({"averages": seed_results["metrics"], "qa_results": seed_results["qa_results"]}, f)

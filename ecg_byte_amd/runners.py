@@ -89,7 +89,8 @@ def validater(model, dataloader, args, epoch):
 
 
 def tester(model, dataloader, tokenizer, args, extra_metrics=None):
-    """inference.py:7-78: batch-1 greedy generation, per-sample metrics, averages over the samples."""
+    """inference.py:7-78: batch-1 greedy generation, per-sample metrics, averages over the samples.  A batch that holds several answers (main's --inference_batch) is
+    generated in one call (model.generate_batch) and still scored sample by sample, in dataset order; a batch whose generation fails scores zero once per sample."""
     model.eval()
     all_results, gt_answers, gen_answers, questions = [], [], [], []
     dev_count = 0
@@ -99,25 +100,37 @@ def tester(model, dataloader, tokenizer, args, extra_metrics=None):
                 print("Skipping invalid batch ")
                 continue
             answer = batch["answer"]
+            n_samples = len(answer) if isinstance(answer, (list, tuple)) and len(answer) > 1 else 1
             out = None
             try:
-                out = [model.generate(batch, tokenizer)]
-                all_results.append(evaluate_strings(answer, out, getattr(args, "device", None), extra_metrics))
-                gt_answers.append(answer[0])
-                gen_answers.append(out[0])
-                questions.append(batch["question"][0])
+                if n_samples > 1:
+                    out = list(model.generate_batch(batch, tokenizer))
+                    if len(out) != n_samples:
+                        raise ValueError(f"generate_batch returned {len(out)} strings for {n_samples} samples")
+                    scored = [evaluate_strings([answer[k]], [out[k]], getattr(args, "device", None), extra_metrics) for k in range(n_samples)]
+                    all_results.extend(scored)
+                    gt_answers.extend(answer)
+                    gen_answers.extend(out)
+                    questions.extend(batch["question"])
+                else:
+                    out = [model.generate(batch, tokenizer)]
+                    all_results.append(evaluate_strings(answer, out, getattr(args, "device", None), extra_metrics))
+                    gt_answers.append(answer[0])
+                    gen_answers.append(out[0])
+                    questions.append(batch["question"][0])
             except Exception as e:
                 print("could not evaluate for some reason:", str(e))
                 print(f"Error type: {type(e).__name__}")
                 # inference.py:34-36: a failed sample scores zero in EVERY metric, so it pulls all the averages down alike
-                zero = {"BLEU": 0}
-                if extra_metrics is not None:
-                    zero.update({"METEOR": 0, "ROUGE": {"rouge-1": 0, "rouge-2": 0, "rouge-l": 0},
-                                 "BERTSCORE": {"hf-prec": [0], "hf-rec": [0], "hf-f1": [0]}})
-                all_results.append(zero)
+                for _ in range(n_samples):
+                    zero = {"BLEU": 0}
+                    if extra_metrics is not None:
+                        zero.update({"METEOR": 0, "ROUGE": {"rouge-1": 0, "rouge-2": 0, "rouge-l": 0},
+                                     "BERTSCORE": {"hf-prec": [0], "hf-rec": [0], "hf-f1": [0]}})
+                    all_results.append(zero)
             if getattr(args, "dev", False):
-                dev_count += 1
-                if dev_count == 10:
+                dev_count += n_samples
+                if dev_count >= 10:
                     break
     sums, counts = {}, {}
     for entry in all_results:

@@ -178,7 +178,9 @@ void ecgb_detokenize_tile(uint32_t *tokens_per_chunk, uint32_t *symbols_per_tile
  * (the reference asserts, data_loader.py:123; the caller checks before the launch).
  * Outputs are batch x row_len: input_ids (int64), attn_mask (float32, 0 where the id equals
  * pad_id), labels (int64, -100 before the answer) and position_ids (int64); inference
- * writes input_ids, attn_mask and lengths_dev only (rows padded with pad_id). */
+ * writes input_ids, attn_mask and lengths_dev only (rows padded with pad_id).
+ * inference == 2: the same prompt right-aligned in its row -- pad_id and mask 0 in FRONT, the
+ * left padding a batched generate() takes; lengths_dev still holds each prompt's length. */
 int ecgb_assemble_hip(const uint32_t *ids_dev, size_t ids_stride, const uint32_t *counts_dev,
                       size_t batch, const int32_t *lut_dev, size_t lut_len,
                       const int32_t *q_ids_dev, const uint32_t *q_offsets_dev,

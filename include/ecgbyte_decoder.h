@@ -181,6 +181,21 @@ int ecgb_gemm_nn_splitk_bf16(const void *a_dev, long long lda, const void *b_dev
 int ecgb_gemm_nt_glu_bf16(const void *a_dev, long long lda, const void *b_dev, long long ldb, const void *a2_dev, long long lda2,
                           const void *b2_dev, long long ldb2, int K2, void *c_dev, long long ldc, void *h_dev, long long ldh,
                           int M, int inter, int K, float alpha, int gelu_tanh, void *stream);
+/* The projections of a batched decode step, 8 < M <= 64 rows (csrc/gemm_rows.hip): C [M, N] = alpha * (A . B^T [+ A2 . B2^T]), fp32 accumulation on
+ * v_mfma_f32_16x16x32_bf16, one rounding to bf16.  B is streamed once, a wave per 16 of its rows, straight into registers; narrow matrices cut K into slices
+ * whose fp32 partials go through scratch_dev and are added in slice order by a second launch (no atomics: the same inputs give the same bits on every launch).
+ * ecgb_gemm_nt_rows_scratch_bytes(M, N, K) is what that takes (0: none, scratch_dev may be null); for the GLU form pass N = 2 * inter.
+ * K % 64 == 0, K2 == 0 (a2_dev / b2_dev ignored) or K2 % 64 == 0, operands 16-byte aligned, lda / ldb / lda2 / ldb2 % 8 == 0, else ECGB_ERR_UNSUPPORTED; any N >= 1 and
+ * ldc >= N.  Rows >= M and columns >= N of C are never written.
+ * _glu: B = [2 * inter, K] (gate rows, then up rows) as in ecgb_gemm_nt_glu_bf16, H [M, inter] = act(gate) * up on the bf16-rounded gate and up -- bit for bit
+ * ecgb_glu_fwd of ecgb_gemm_nt_rows_bf16's result; gate|up is never written. */
+size_t ecgb_gemm_nt_rows_scratch_bytes(int M, int N, int K);
+int ecgb_gemm_nt_rows_bf16(const void *a_dev, long long lda, const void *b_dev, long long ldb, const void *a2_dev, long long lda2,
+                           const void *b2_dev, long long ldb2, int K2, void *c_dev, long long ldc, int M, int N, int K, float alpha,
+                           void *scratch_dev, size_t scratch_bytes, void *stream);
+int ecgb_gemm_nt_rows_glu_bf16(const void *a_dev, long long lda, const void *b_dev, long long ldb, const void *a2_dev, long long lda2,
+                               const void *b2_dev, long long ldb2, int K2, void *h_dev, long long ldh, int M, int inter, int K, float alpha,
+                               int gelu_tanh, void *scratch_dev, size_t scratch_bytes, void *stream);
 /* Weight-gradient product without transposed copies: C[N,K] = alpha * A^T . B with A = [M,N] and B = [M,K]
  * row-major (dW = dY^T . X, the contraction index is the row index of both operands).  M % 64 == 0.
  * splits == 1: C is bf16.  splits > 1: the contraction is cut into `splits` slices run by separate workgroups
