@@ -193,6 +193,7 @@ constexpr int INPUT_F64 = 0, INPUT_BYTES = 1;
 constexpr uint32_t kLenBias = 30;          // flow kernel: a symbol byte >= kLenBias holds kLenBias + the length of the token that starts there
 constexpr int kStageGroups = 5;             // groups of 4 samples a lane loads before it classifies the first (C2: 3 batches per segment)
 constexpr uint32_t kListRegs = 8;          // flow kernel: token-list entries a lane keeps in registers between its two sweeps
+constexpr uint32_t kResolveLead = 2;       // flow kernel: blocks ahead of its own at which a lane's first chain walk starts (resolve; measured 0 / 1 / 2: EXPERIMENTS.md R10)
 constexpr size_t kFlowSlot = 8192;         // token-list entries (u32: position | id << 16) per resident wave of the flow kernel: one segment
 
 // LDS byte address of word (i >> 5) of a table of 1 << SHIFT bytes per 32 entries: two instructions (the compiler's own
@@ -713,8 +714,9 @@ __global__ __launch_bounds__(1024) void encode_flow_kernel(EncodeArgs A)
                 if (v) first_claimed = pbase + 32 * k + (uint32_t)__ffs(v) - 1u;
                 n_list += (uint32_t)__popc(v);
             }
-            // every claimed position got exactly one list entry (its claimant emitted the token that starts there), so the
-            // length of the list is the population of the claim bitmap -- the parse loop keeps its own count in a scalar
+            // every claimed position got exactly one list entry (its claimant emitted the token that starts there), so the length of the list
+            // is the population of the claim bitmap.  (The parse loop's own count, tok_tail - tok_list, is complete only in the lane that left
+            // the loop last: reading it here costs the loop a vector copy of the scalar every trip.)
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) n_list += (uint32_t)__shfl_xor(n_list, d, 64);
             // the first kListRegs * 64 entries of the list (all of it unless the segment is mostly two-symbol tokens) are read
@@ -745,9 +747,30 @@ __global__ __launch_bounds__(1024) void encode_flow_kernel(EncodeArgs A)
                 }
                 return p;
             };
+            // The first claimed position of a block is very often the start of a speculative prefix, which meets the real chain a few tokens on
+            // (a block holds about five tokens).  So the first walk starts up to kResolveLead blocks early, at the first claimed position of the
+            // farthest of those blocks that holds one, and has almost always joined the real chain by the time it enters its own block: the
+            // correction loop below, a divergent re-walk of one more lane per pass, then mostly finds nothing to correct.  Any guess is valid --
+            // the loop ends at the same fixed point.  Blocks ahead without a claimed position (a token longer than a block covers them, or they
+            // lie before the carry): the lane's own first claimed position, as before.
             unsigned long long chain = 0, chain_hi = 0;
             uint32_t entry = (c == 0) ? carry_rel : first_claimed;
             entry = max(entry, s_blk);
+            if constexpr (kResolveLead > 0) {
+                uint32_t ahead = first_claimed, from = 0xFFFFFFFFu;
+#pragma unroll
+                for (uint32_t d = 1; d <= kResolveLead; ++d) {
+                    ahead = __shfl_up(ahead, 1, 64);                                         // first_claimed of lane c - d, whose block ends at ...
+                    if (c >= d && ahead < min(pbase - (d - 1) * PW, seg_len)) from = ahead;
+                }
+                if (from != 0xFFFFFFFFu && pbase < seg_len) {
+                    while (from < s_blk) {                                                   // the chain bits of these blocks are their owners'
+                        const uint32_t bb = sym[from];
+                        from += (bb < kLenBias) ? 1u : bb - kLenBias;
+                    }
+                    entry = from;
+                }
+            }
             uint32_t my_exit = follow(entry, chain, chain_hi);
             PROF_STAMP(7);
             for (;;) {

@@ -1,11 +1,11 @@
 """Event simulation of the claim-merge parse: 64 lanes in lockstep, one step or one emit per iteration, dynamic chunk tasks."""
 import os, sys, pickle, json
 import numpy as np
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
 sys.path.insert(0, ROOT)
 from oracle import oracle as O
 import importlib.util
-spec = importlib.util.spec_from_file_location("synth", os.path.join(ROOT, "ecg-byte_amd", "synth.py")); synth = importlib.util.module_from_spec(spec); spec.loader.exec_module(synth)
+spec = importlib.util.spec_from_file_location("synth", os.path.join(ROOT, "ecg_byte_amd", "synth.py")); synth = importlib.util.module_from_spec(spec); spec.loader.exec_module(synth)
 G = os.path.join(ROOT, "tests", "golden")
 vocab, merges = pickle.load(open(os.path.join(G, "tokenizer_c2.pkl"), "rb"))
 pct = json.load(open(os.path.join(G, "percentiles_c2.json")))

@@ -1,5 +1,6 @@
 """Dev-only: phase timers of encode_flow_kernel from the -DECGB_PROFILE build (make -C ecg_byte_amd/csrc prof): clock64 ticks of every wave's lane 0, summed per workgroup,
-for the bench batch (4 096 records of 12 x 5000, C2 tokenizer).  Phases: 0 stage + run map, 1 parse, 6 / 7 / 2 resolve (lengths, chain, prefix counts), 3 emit."""
+for the bench batch (4 096 records of 12 x 5000, C2 tokenizer).  Phases: 0 stage + run map, 1 parse, 6 / 7 / 2 resolve (lengths into the symbol bytes, every lane's first chain walk with its lead-in, the correction loop), 3 emit
+(prefix counts and the second sweep of the list).  Counter 4: passes of the correction loop; counter 5: trips of the parse loop."""
 import os, sys, ctypes
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -24,8 +25,9 @@ ids, counts = tok.quantize_encode(x, pc, ids_stride=8192)
 torch.cuda.synchronize()
 L.ecgb_debug_set_profile_buffer(ctypes.c_void_p(0))
 p = prof.view(-1, 8).sum(0).cpu().numpy().astype(np.float64)
-names = {0: "stage + run map", 1: "parse", 6: "resolve: lengths", 7: "resolve: chain", 2: "resolve: prefix counts", 3: "emit"}
+names = {0: "stage + run map", 1: "parse", 6: "resolve: lengths", 7: "resolve: chain", 2: "resolve: correction loop", 3: "emit"}
 tot = sum(p[k] for k in names)
 print(f"tokens {int(counts.sum())}, ticks per record {tot / B:.0f}")
 for k, nm in names.items(): print(f"  {nm:26s} {100 * p[k] / tot:5.1f} %")
-print("  counters [4], [5]:", p[4], p[5])
+n_seg = B * -(-12 * 5000 // int(os.environ.get("SEG", "3456")))      # segments of the bench plan (16 waves: 54-symbol chunks)
+print(f"  correction passes per segment {p[4] / n_seg:.2f} (counter 4: {p[4]:.0f}), parse trips per record {p[5] / B:.0f}")
