@@ -295,20 +295,43 @@ __device__ __forceinline__ void stage_symbols(uint8_t *sym, uint32_t stage_len, 
 // ---- change map: bit k of `dmap` = (class of position k != class of position k - 1), bit 0 set.  A run of
 // equal symbols is a run of zero bits, so the walk reads the length of the run ahead of it with one
 // find-first-set instead of one trie step per symbol.
+//
+// Eight symbols a step.  Every class is below 32 (tokenizer.hpp: kOtherClass = 29 is the largest), so every byte of
+// x = v ^ (the same symbols one position earlier) is below 64, and x + 0x3F3F3F3F sets bit 6 of a byte exactly when the byte
+// is non-zero, without a carry into the next byte (0x3F + 0x3F < 0x80): no masking before the add, no `| x` behind it.  The
+// earlier symbols are one byte-align of the word and the word before it.  The bits 6 of the first word go to bit 2 of their
+// bytes, beside the second word's at bit 6: eight flags at bits 2 + 4m, which two shift-ors gather into bits 23..30
+// (z | z << 7 | z << 14 | z << 21: the first word's flags, from bits 2, 10, 18, 26, land on 23..26, the second word's, from 6, 14, 22, 30, on
+// 27..30; the other three terms of each of those bits are positions that are not 2 mod 4, where z holds nothing).
+// The byte before word 0 is 0x20, no class, so bit 0 of the map is set.
+// Bytes that are no classes: the last word of the map may reach up to 16 bytes past stage_len (a multiple of 16, rounded up to 32 here), where the
+// buffer can still hold length bytes (31..255) of an earlier segment or record.  There the add does carry -- but only upwards, into bytes of later
+// positions, so every bit below stage_len is exact; the bits at and past stage_len depend on stale bytes (as they did with the general byte test)
+// and are never consumed: a walk stops at the sentinel class, which lies below stage_len.
+__device__ __forceinline__ uint32_t change_bits8(uint32_t before, uint32_t v0, uint32_t v1)
+{
+    const uint32_t x0 = v0 ^ __builtin_amdgcn_alignbyte(v0, before, 3);
+    const uint32_t x1 = v1 ^ __builtin_amdgcn_alignbyte(v1, v0, 3);
+    const uint32_t y0 = x0 + 0x3F3F3F3Fu, y1 = x1 + 0x3F3F3F3Fu;
+    uint32_t z = ((y0 >> 4) & 0x04040404u) | (y1 & 0x40404040u);
+    z |= z << 7;
+    z |= z << 14;
+    return (z >> 23) & 0xFFu;
+}
+
 template <int CHUNK>
 __device__ __forceinline__ void build_dmap(const uint8_t *sym, uint32_t *dmap, uint32_t stage_len, uint32_t lane, uint32_t nlanes)
 {
     const uint32_t n_words = (stage_len + 31) >> 5;
     for (uint32_t w = lane; w < n_words; w += nlanes) {
-        uint32_t prev = (w == 0) ? 0xFFu : sym[swz<CHUNK>(32 * w - 1)];   // 0xFF is no class: bit 0 of word 0 is set
+        uint32_t before = (w == 0) ? 0x20000000u : (uint32_t)sym[swz<CHUNK>(32 * w - 1)] << 24;   // only its top byte is used
         uint32_t bits = 0;
 #pragma unroll
-        for (uint32_t g = 0; g < 8; ++g) {
-            const uint32_t v = *reinterpret_cast<const uint32_t *>(sym + swz<CHUNK>(32 * w + 4 * g));
-            const uint32_t x = v ^ ((v << 8) | prev);                                  // byte t != 0 iff symbol t differs from t - 1
-            const uint32_t nz = ((((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) >> 7) & 0x01010101u;   // bit 8t = byte t non-zero
-            bits |= ((nz | (nz >> 7) | (nz >> 14) | (nz >> 21)) & 0xFu) << (4 * g);
-            prev = v >> 24;
+        for (uint32_t g = 0; g < 8; g += 2) {
+            const uint32_t v0 = *reinterpret_cast<const uint32_t *>(sym + swz<CHUNK>(32 * w + 4 * g));
+            const uint32_t v1 = *reinterpret_cast<const uint32_t *>(sym + swz<CHUNK>(32 * w + 4 * g + 4));
+            bits |= change_bits8(before, v0, v1) << (4 * g);
+            before = v1;
         }
         dmap[w] = bits;
     }
@@ -565,22 +588,20 @@ __global__ __launch_bounds__(1024) void encode_flow_kernel(EncodeArgs A)
 
             // ---- chunk starts: equal numbers of RUNS per lane, not of symbols (a flat stretch costs a step per ~30
             // symbols, a flickering one a step per symbol).  Lane l counts the run starts in positions [64l, 64l+64),
-            // a wave scan ranks them, and chunk k begins at the run start of rank k*R/64.  The claim bitmap is not in use
-            // yet and holds the 64 starts for a moment.  Any start is valid (claims make the parse exact whatever the
-            // starts are); the balance is what this buys.
+            // a wave scan ranks them, and chunk k begins at the run start of rank k*R/64.  Any start is valid (claims make
+            // the parse exact whatever the starts are); the balance is what this buys.
             const uint32_t carry_rel = carry - seg_base;
             uint32_t my_start = c * CH;
             {
                 const uint32_t p0 = PW * c;                                     // this lane's positions [p0, p0 + PW)
-                uint32_t bw[WPL], nw[WPL], n_l = 0;
+                uint32_t bw[WPL], n_l = 0;
 #pragma unroll
                 for (uint32_t k = 0; k < WPL; ++k) {
                     const uint32_t q0 = p0 + 32 * k;
                     uint32_t v = (q0 < seg_len) ? dmap[WPL * c + k] : 0u;
                     if (q0 < seg_len && seg_len - q0 < 32) v &= (1u << (seg_len - q0)) - 1u;
                     bw[k] = v;
-                    nw[k] = (uint32_t)__popc(v);
-                    n_l += nw[k];
+                    n_l += (uint32_t)__popc(v);
                 }
                 uint32_t incl = n_l;
 #pragma unroll
@@ -588,34 +609,33 @@ __global__ __launch_bounds__(1024) void encode_flow_kernel(EncodeArgs A)
                     const uint32_t t = __shfl_up(incl, d, 64);
                     if (c >= (uint32_t)d) incl += t;
                 }
-                const uint32_t R = __shfl(incl, 63, 64), P = incl - n_l;
-                marks[c] = my_start;                                            // fallback: equal symbol counts
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                if (n_l) {
-                    const float inv = 64.0f / (float)R;
-                    uint32_t k = max((uint32_t)ceilf((float)P * inv), 1u);
-                    const uint32_t k_hi = min((uint32_t)ceilf((float)(P + n_l) * inv), 64u);
-                    for (; k < k_hi; ++k) {
-                        const uint32_t t = (k * R) >> 6;
-                        if (t < P || t >= P + n_l) continue;
-                        uint32_t want = t - P, w = bw[0], pos = 0;              // the want-th (0-based) set bit of the lane's words
+                // Chunk c looks its start up itself: the rank it wants, a binary search over the lanes' inclusive counts for the lane whose block
+                // holds the run start of that rank (six shuffles), that lane's words, one bit select.  (Every lane used to select the starts that
+                // fall into its own block and pass them through LDS: a loop as long as the wave's densest block, four to seven selects.)
+                const uint32_t R = __shfl(incl, 63, 64);
+                if (R) {                                                        // (wave-uniform; bit 0 of the map is set, so R > 0 whenever seg_len > 0)
+                    const uint32_t t = (c * R) >> 6;                            // < R
+                    uint32_t owner = 0;                                         // lanes whose inclusive count is <= t: the owner is the first above
 #pragma unroll
-                        for (uint32_t q = 0; q + 1 < WPL; ++q)
-                            if (pos == 32 * q && want >= nw[q]) { want -= nw[q]; w = bw[q + 1]; pos = 32 * (q + 1); }
+                    for (uint32_t half = 32; half > 0; half >>= 1)
+                        if ((uint32_t)__shfl(incl, (int)(owner + half - 1u), 64) <= t) owner += half;
+                    uint32_t want = t - (uint32_t)__shfl(incl - n_l, (int)owner, 64);   // the want-th (0-based) set bit of the owner's words
+                    uint32_t ow[WPL];
 #pragma unroll
-                        for (int sh = 16; sh >= 1; sh >>= 1) {
-                            const uint32_t below = (uint32_t)__popc(w & ((1u << sh) - 1u));
-                            if (want >= below) { want -= below; w >>= sh; pos += sh; }
-                        }
-                        marks[k] = p0 + pos;
+                    for (uint32_t q = 0; q < WPL; ++q) ow[q] = (uint32_t)__shfl(bw[q], (int)owner, 64);
+                    uint32_t w = ow[0], pos = 0;
+#pragma unroll
+                    for (uint32_t q = 0; q + 1 < WPL; ++q) {
+                        const uint32_t nq = (uint32_t)__popc(ow[q]);
+                        if (pos == 32 * q && want >= nq) { want -= nq; w = ow[q + 1]; pos = 32 * (q + 1); }
                     }
+#pragma unroll
+                    for (int sh = 16; sh >= 1; sh >>= 1) {
+                        const uint32_t below = (uint32_t)__popc(w & ((1u << sh) - 1u));
+                        if (want >= below) { want -= below; w >>= sh; pos += sh; }
+                    }
+                    my_start = PW * owner + pos;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                my_start = marks[c];
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
             }
             for (uint32_t w = c; w < MARKW; w += 64) marks[w] = 0;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -738,14 +758,17 @@ __global__ __launch_bounds__(1024) void encode_flow_kernel(EncodeArgs A)
             PROF_STAMP(6);
 
             auto follow = [&](uint32_t p, unsigned long long &lo, unsigned long long &hi) {   // length pointers through this lane's block
+                // the hop counts from the block's first position: the bit index is the loop variable itself.  A byte below kLenBias is a
+                // symbol (one position), a length byte is at least kLenBias + 1: max(byte, kLenBias + 1) - kLenBias is the step of both
                 lo = 0; hi = 0;
-                while (p < e_blk) {
-                    const uint32_t rel = p - pbase;
+                const uint8_t *blk = sym + pbase;
+                const uint32_t e_rel = e_blk - s_blk;       // 0 for a lane past the segment (s_blk = e_blk = seg_len), else s_blk = pbase <= p
+                uint32_t rel = p - pbase;
+                while (rel < e_rel) {
                     if (!WIDE || rel < 64) lo |= 1ull << rel; else hi |= 1ull << (rel - 64);
-                    const uint32_t bb = sym[p];
-                    p += (bb < kLenBias) ? 1u : bb - kLenBias;
+                    rel += max((uint32_t)blk[rel], kLenBias + 1u) - kLenBias;
                 }
-                return p;
+                return e_rel ? pbase + rel : p;
             };
             // The first claimed position of a block is very often the start of a speculative prefix, which meets the real chain a few tokens on
             // (a block holds about five tokens).  So the first walk starts up to kResolveLead blocks early, at the first claimed position of the
@@ -765,8 +788,7 @@ __global__ __launch_bounds__(1024) void encode_flow_kernel(EncodeArgs A)
                 }
                 if (from != 0xFFFFFFFFu && pbase < seg_len) {
                     while (from < s_blk) {                                                   // the chain bits of these blocks are their owners'
-                        const uint32_t bb = sym[from];
-                        from += (bb < kLenBias) ? 1u : bb - kLenBias;
+                        from += max((uint32_t)sym[from], kLenBias + 1u) - kLenBias;
                     }
                     entry = from;
                 }
