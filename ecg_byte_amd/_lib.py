@@ -241,6 +241,8 @@ def lib():
         "ecgb_attn_fwd": [vp, ll, vp, ll, vp, ll, vp, vp, ll, vp, ci, ci, ci, ci, ci, f32, vp],
         "ecgb_attn_probs": [vp, ll, vp, ll, vp, vp, vp, vp, f32, ci, ci, ci, ci, ci, ci, f32, vp],
         "ecgb_attn_bwd": [vp, ll, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp, vp, ll, vp, ll, vp, ll, ci, ci, ci, ci, ci, f32, vp, sz, vp],
+        "ecgb_attn_fwd_dropout": [vp, ll, vp, ll, vp, ll, vp, vp, ll, vp, ci, ci, ci, ci, ci, f32, f32, C.c_uint64, vp],
+        "ecgb_attn_bwd_dropout": [vp, ll, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp, vp, ll, vp, ll, vp, ll, ci, ci, ci, ci, ci, f32, vp, sz, f32, C.c_uint64, vp],
         "ecgb_attn_bwd_rope": [vp, ll, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp, vp, ll, vp, ll, vp, ll, vp, vp, ci, ci, ci, ci, ci, f32, vp, sz, vp],
     }
     for name, args in sigs.items():

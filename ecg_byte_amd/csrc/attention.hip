@@ -17,14 +17,25 @@
 // (h = lane >> 5), and the transposed LDS tile is read in that same k order (two 8-byte reads).
 // The backward kernels reuse the scheme with the roles permuted (lanes = queries for dQ, lanes = keys
 // for dK/dV, which loops over the query heads of its KV group, so no atomics anywhere).
+//
+// DROP (head_dim 64, the register-staged kernels): inverted dropout on the probabilities (GPT-2's attn_dropout), ecgb_attn_fwd_dropout / ecgb_attn_bwd_dropout.
+// Element (b, hq, query i, key j) is kept iff mix32(seed, ((b Hq + hq) S + i) S + j) >= p 2^32 -- ecgb_dropout_bf16's rule on a contiguous [B Hq, S, S] tensor --
+// evaluated again wherever it is needed, never stored.  Z = kept / (1 - p):
+//   forward   o = (P o Z) V: only the bf16 operand of the P.V product is masked (row maximum, row sum and lse are the undropped ones), 1 / (1 - p) rides on the
+//             final row scale;
+//   backward  delta = rowsum(dO o O) with that O, dP = (dO V^T) o Z, dS = P o (dP - delta) scale, dV = (P o Z)^T dO.
+// The hash's argument is linear in the index, so its per-lane part (the row for forward / dQ, the key for dK / dV, and the lane half's 4 h offset inside a tile)
+// is formed once per kernel, the tile's part once per tile (uniform), and an element adds a constant: mix32_finish -- two 64-bit multiplies -- per score is what is left.
 #include "attention_common.inc"
+#include "dropout_math.hpp"
 
 namespace {
 
-template <int D, bool DMA = false>
+template <int D, bool DMA = false, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs A)
 {
     static_assert(!DMA || D == 64, "the LDS-DMA staging is written for 128-byte rows");
+    static_assert(!DROP || (D == 64 && !DMA), "dropout on the probabilities: head_dim 64, register-staged");
     // two K / V^T tile buffers: the tile after the one being multiplied is written while the others still compute,
     // one barrier per tile.  Dynamic LDS (4 x 128 D bytes + 4 bytes per key: 36 KB at head_dim 64 and S 1024, 139 KB at 256 / 2048).
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -43,6 +54,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs A)
     const unsigned short *Q = A.q + (long long)hq * D, *K = A.k + (long long)g * D, *V = A.v + (long long)g * D;
     bf16x8 qf[D / 16];
     load_row_frags<D>(qf, Q, A.ldq, rowbase + qi, qvalid, h);
+    unsigned long long drop_row = 0;                         // DROP: the hash argument of (this lane's row, key 4 h)
+    if constexpr (DROP) drop_row = A.drop_seed + (unsigned long long)((((long long)b * A.Hq + hq) * A.S + qi) * A.S + 4 * h) * kMixStep;
     f32x16 accO[D / 32];
 #pragma unroll
     for (int db = 0; db < D / 32; ++db)
@@ -211,6 +224,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs A)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) accO[db][r] *= alpha;
                 }
+                if constexpr (DROP) {                               // the row sum above is the undropped one; the P.V operand below loses the dropped keys
+                    const unsigned long long zt = drop_row + (unsigned long long)k0 * kMixStep;
+#pragma unroll
+                    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (mix32_finish(zt + (unsigned long long)(kb * 32 + (r & 3) + 8 * (r >> 2)) * kMixStep) < A.drop_thr) p[kb][r] = 0.f;
+                }
                 APROF(2);
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
@@ -247,16 +268,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs A)
         for (int k = 0; k < 7; ++k) atomicAdd(&g_attn_prof[(threadIdx.x >> 6) * 8 + k], prof_acc[k]);
 #endif
     const float lt = l + __shfl_xor(l, 32, 64);
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
+    float inv = lt > 0.f ? 1.f / lt : 0.f;
+    if constexpr (DROP) inv *= A.drop_inv;
     store_accT<D / 32>(accO, A.o + (long long)hq * D, A.ldo, rowbase + qi, qvalid, h, inv);
     if (qvalid && h == 0) A.lse[((long long)b * A.Hq + hq) * A.S + qi] = lt > 0.f ? m + log2f(lt) : INFINITY;
 }
 
 // =====================================================================================================
 // backward, dQ (and delta): 1-D grid of ceil(S/128) x Hq x B workgroups (map_block); lanes = queries
-template <int D>
+template <int D, bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs A)
 {
+    static_assert(!DROP || D == 64, "dropout on the probabilities: head_dim 64");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // 3 x 128 D bytes + 4 bytes per key
     constexpr int kTile = 128 * D;
     unsigned char *lds_k = smem, *lds_v = smem + kTile, *lds_kt = smem + 2 * kTile;
@@ -283,6 +306,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs A)
     const long long stat = ((long long)b * A.Hq + hq) * A.S + qi;
     if (qvalid && h == 0) A.delta[stat] = delta;
     const float lse = qvalid ? A.lse[stat] : INFINITY;
+    unsigned long long drop_row = 0;                         // DROP: the hash argument of (this lane's row, key 4 h)
+    if constexpr (DROP) drop_row = A.drop_seed + (unsigned long long)(stat * A.S + 4 * h) * kMixStep;
     f32x16 accQ[D / 32];
 #pragma unroll
     for (int db = 0; db < D / 32; ++db)
@@ -326,6 +351,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs A)
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_plain<D>(lds_v, kb * 32 + lr, ks, h), dof[ks], dp, 0, 0, 0);
             }
             float ds[16];
+            if constexpr (DROP) {                                   // dP = (dO V^T) o Z
+                const unsigned long long zt = drop_row + (unsigned long long)k0 * kMixStep;
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    dp[r] *= mix32_finish(zt + (unsigned long long)(kb * 32 + (r & 3) + 8 * (r >> 2)) * kMixStep) >= A.drop_thr ? A.drop_inv : 0.f;
+            }
             if (need_mask) {
                 float4 mk4[4];
 #pragma unroll
@@ -485,9 +516,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_dma_kernel(AttnArgs A)
 // each with full-width accumulators: the dV pass needs S alone (K fragments), the dK pass S and dP (K and V fragments), 1.25 x the MFMA
 // work of a single pass instead of the 2.5 x of splitting the d range four ways (DS = 4, the first head_dim-256 version: 3.3 ms per
 // layer at Gemma-2B's shape).
-template <int D, int DS, int WHICH>
+template <int D, int DS, int WHICH, bool DROP = false>
 __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs &A, const int block_x, const int b, const int g, const int hsplit = 0)
 {
+    static_assert(!DROP || (D == 64 && DS == 1 && WHICH == 0), "dropout on the probabilities: head_dim 64, one pass");
     constexpr bool DO_V = WHICH != 2, DO_K = WHICH != 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // 4 x 128 D bytes + 512
     constexpr int kTile = 128 * D;
@@ -504,6 +536,12 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs &A, const int b
     load_row_frags<D>(kf, A.k + (long long)g * D, A.ldk, rowbase + ki, kvalid, h);
     if constexpr (DO_K) load_row_frags<D>(vf, A.v + (long long)g * D, A.ldv, rowbase + ki, kvalid, h);
     const bool kvis = kvalid && A.mask[rowbase + (kvalid ? ki : 0)] != 0.f;
+    // DROP: the hash argument of (query 4 h, this lane's key); a query row further is drop_qstep more
+    unsigned long long drop_key = 0, drop_qstep = 0;
+    if constexpr (DROP) {
+        drop_qstep = (unsigned long long)A.S * kMixStep;
+        drop_key = A.drop_seed + (unsigned long long)(4ll * h * A.S + ki) * kMixStep;
+    }
     f32x16 accK[NB], accV[NB];
 #pragma unroll
     for (int db = 0; db < NB; ++db)
@@ -571,6 +609,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs &A, const int b
                 if constexpr (DO_K) dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_plain<D>(lds_do, qb * 32 + lr, ks, h), vf[ks], dp, 0, 0, 0);
             }
             float pr[16], ds[16];
+            unsigned long long zt = 0;                                       // DROP: (the head's first row + the tile's first query, this lane's key)
+            if constexpr (DROP) zt = drop_key + (unsigned long long)(stat + t0) * drop_qstep;
             const bool diag = t0 + qb * 32 < wave_kmin + 32;              // some query of the block may precede some key of the wave
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {                                // the lane's 16 queries are 4 runs of 4: 16-byte reads
@@ -583,8 +623,14 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnArgs &A, const int b
                     const int ql = qb * 32 + t + 8 * g4 + 4 * h;             // query inside the tile
                     const bool vis = kvis & (!diag | (ki <= t0 + ql));
                     const float e = vis ? fast_exp2(__builtin_fmaf(s[r], sc, -lse_t[t])) : 0.f;
-                    pr[r] = e;
-                    ds[r] = e * (dp[r] - dl_t[t]) * A.scale;
+                    if constexpr (DROP) {                                    // dV takes P o Z, dS the undropped P and dP o Z
+                        const float z = mix32_finish(zt + (unsigned long long)(qb * 32 + t + 8 * g4) * drop_qstep) >= A.drop_thr ? A.drop_inv : 0.f;
+                        pr[r] = e * z;
+                        ds[r] = e * (dp[r] * z - dl_t[t]) * A.scale;
+                    } else {
+                        pr[r] = e;
+                        ds[r] = e * (dp[r] - dl_t[t]) * A.scale;
+                    }
                 }
             }
 #pragma unroll
@@ -1374,12 +1420,12 @@ __global__ __launch_bounds__(NW * 64, ECGB_LEAN_DKV_WGS) void attn_bwd_dkv_lean_
     }
 }
 
-template <int D, int DS, int WHICH = 0>
+template <int D, int DS, int WHICH = 0, bool DROP = false>
 __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void attn_bwd_dkv_kernel(AttnArgs A)   // head_dim 64: two waves per SIMD (<= 256 registers)
 {
     int blk, head_in, group;
     map_block((int)blockIdx.x, ((A.S + 127) / 128) * DS, 1, A.B * A.Hkv, false, blk, head_in, group);   // key block 0 sees every query: first
-    attn_bwd_dkv_body<D, DS, WHICH>(A, blk, group / A.Hkv, group % A.Hkv);
+    attn_bwd_dkv_body<D, DS, WHICH, DROP>(A, blk, group / A.Hkv, group % A.Hkv);
 }
 // head_dim 256: the dV pass and the dK pass of a key block as two workgroups of ONE launch (even / odd blockIdx.x) -- Gemma's single KV
 // head gives only S / 128 x batch key blocks, half a chip's worth at C5's shape
@@ -1710,6 +1756,41 @@ extern "C" int ecgb_attn_fwd(const void *q_dev, long long ldq, const void *k_dev
 }
 
 namespace {
+// what ecgb_attn_fwd_dropout / ecgb_attn_bwd_dropout ask of (p, head_dim) before anything is launched; 1: p == 0, the plain entry point serves the call
+int check_drop(float p, int head_dim, const char *who)
+{
+    if (!(p >= 0.f && p < 1.f)) { ecgb::set_error(std::string(who) + ": 0 <= p < 1 required"); return ECGB_ERR_INVALID; }
+    if (p == 0.f) return 1;
+    if (head_dim != 64) { ecgb::set_error(std::string(who) + ": dropout on the probabilities is built for head_dim 64 only"); return ECGB_ERR_UNSUPPORTED; }
+    return ECGB_OK;
+}
+void set_drop(AttnArgs &A, float p, uint64_t seed)
+{
+    A.drop_seed = (unsigned long long)seed;
+    A.drop_thr = drop_threshold(p);
+    A.drop_inv = 1.0f / (1.0f - p);                          // (as ecgb_dropout_bf16 forms it)
+}
+}  // namespace
+
+extern "C" int ecgb_attn_fwd_dropout(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
+                                     const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
+                                     int n_q_heads, int n_kv_heads, int head_dim, float scale, float p, uint64_t seed, void *stream)
+{
+    int rc = check_drop(p, head_dim, "ecgb_attn_fwd_dropout");
+    if (rc == 1) return ecgb_attn_fwd(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, ldo, lse_dev, batch, seq, n_q_heads, n_kv_heads, head_dim, scale, stream);
+    if (rc) return rc;
+    AttnArgs A = {};
+    A.q = (const unsigned short *)q_dev; A.k = (const unsigned short *)k_dev; A.v = (const unsigned short *)v_dev;
+    A.ldq = ldq; A.ldk = ldk; A.ldv = ldv; A.mask = attn_mask_dev; A.o = (unsigned short *)o_dev; A.ldo = ldo; A.lse = lse_dev;
+    A.B = batch; A.S = seq; A.Hq = n_q_heads; A.Hkv = n_kv_heads; A.scale = scale;
+    set_drop(A, p, seed);
+    rc = check_args(A, head_dim, "ecgb_attn_fwd_dropout");
+    if (rc) return rc;
+    const dim3 grid((unsigned)((seq + 127) / 128) * (unsigned)n_q_heads * (unsigned)batch);
+    return launch_attn(attn_fwd_kernel<64, false, true>, grid, dim3(256), 4 * 128 * 64 + 4 * ((seq + 63) & ~63), stream, A, "attn_fwd_kernel<64, dropout>");
+}
+
+namespace {
 // head_dim 256 with few (batch, KV head, key block) workgroups: the causal key blocks differ 16-fold in work and one launch of <= 256
 // workgroups takes as long as its heaviest one (key block 0).  Splitting a group's query heads over 2..4 workgroups gives the scheduler
 // pieces to balance with (heaviest first); the price is fp32 partial slabs and a small ordered reduction.
@@ -1835,6 +1916,37 @@ extern "C" int ecgb_attn_bwd(const void *q_dev, long long ldq, const void *k_dev
 {
     return attn_bwd_impl(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, do_dev, ldo, lse_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv,
                          batch, seq, n_q_heads, n_kv_heads, head_dim, scale, scratch_dev, scratch_bytes, stream, nullptr, nullptr);
+}
+
+// the backward of ecgb_attn_fwd_dropout (o_dev and lse_dev are that forward's): two launches of the register-staged kernels' DROP forms; the scratch is not used
+extern "C" int ecgb_attn_bwd_dropout(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
+                                     const float *attn_mask_dev, const void *o_dev, const void *do_dev, long long ldo,
+                                     const float *lse_dev, float *delta_dev, void *dq_dev, long long lddq, void *dk_dev, long long lddk,
+                                     void *dv_dev, long long lddv, int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                                     float scale, void *scratch_dev, size_t scratch_bytes, float p, uint64_t seed, void *stream)
+{
+    int rc = check_drop(p, head_dim, "ecgb_attn_bwd_dropout");
+    if (rc == 1) return ecgb_attn_bwd(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, do_dev, ldo, lse_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv,
+                                      batch, seq, n_q_heads, n_kv_heads, head_dim, scale, scratch_dev, scratch_bytes, stream);
+    if (rc) return rc;
+    AttnArgs A = {};
+    A.q = (const unsigned short *)q_dev; A.k = (const unsigned short *)k_dev; A.v = (const unsigned short *)v_dev;
+    A.ldq = ldq; A.ldk = ldk; A.ldv = ldv; A.mask = attn_mask_dev; A.o = (unsigned short *)const_cast<void *>(o_dev); A.ldo = ldo;
+    A.lse = const_cast<float *>(lse_dev); A.d_o = (const unsigned short *)do_dev; A.delta = delta_dev;
+    A.dq = (unsigned short *)dq_dev; A.dk = (unsigned short *)dk_dev; A.dv = (unsigned short *)dv_dev;
+    A.lddq = lddq; A.lddk = lddk; A.lddv = lddv;
+    A.B = batch; A.S = seq; A.Hq = n_q_heads; A.Hkv = n_kv_heads; A.scale = scale;
+    A.head_splits = 1;
+    set_drop(A, p, seed);
+    rc = check_args(A, head_dim, "ecgb_attn_bwd_dropout");
+    if (rc) return rc;
+    if (lddq % 4 || lddk % 4 || lddv % 4) { ecgb::set_error("ecgb_attn_bwd_dropout: gradient row strides must be multiples of 4"); return ECGB_ERR_UNSUPPORTED; }
+    const unsigned nblk = (unsigned)((seq + 127) / 128);
+    rc = launch_attn(attn_bwd_dq_kernel<64, true>, dim3(nblk * (unsigned)n_q_heads * (unsigned)batch), dim3(256), 3 * 128 * 64 + 4 * ((seq + 63) & ~63), stream, A,
+                     "attn_bwd_dq_kernel<64, dropout>");
+    if (rc) return rc;
+    return launch_attn(attn_bwd_dkv_kernel<64, 1, 0, true>, dim3(nblk * (unsigned)n_kv_heads * (unsigned)batch), dim3(256), 4 * 128 * 64 + 512, stream, A,
+                       "attn_bwd_dkv_kernel<64, dropout>");
 }
 
 // ecgb_attn_bwd followed by RoPE's backward on dQ and dK (ecgb_rope, inverse), in the attention kernels' own stores: q and k are the ROTATED projections the forward

@@ -32,6 +32,11 @@ struct AttnArgs {
     // head_dim 256, round 6: the dK pass leaves its probabilities P (bf16, as the fragments of the products that use them) here and a dV kernel of its own reads them instead of
     // forming the scores a second time: [B][Hq][key block of 128][64-query tile][wave][query half][k-step][lane] 16-byte pieces, B * Hq * S^2 bf16 in all (null: the pair kernel)
     unsigned short *pbuf = nullptr;
+    // the kernels with dropout on the probabilities (attention.hip, DROP): element (b, hq, i, j) is kept iff mix32(drop_seed, ((b Hq + hq) S + i) S + j) >= drop_thr
+    // (dropout_math.hpp), kept elements weigh drop_inv = 1 / (1 - p).  At the end: the other kernels' arguments stay where they were
+    unsigned long long drop_seed = 0;
+    unsigned drop_thr = 0;
+    float drop_inv = 1.f;
 };
 // attention_d256.hip (round 6): the head_dim-256 backward kernels whose LDS reads the compiler schedules.  Each sets the dynamic-LDS attribute, launches and reports like
 // launch_attn(); `seq` sizes the key mask in LDS.

@@ -14,6 +14,7 @@
 
 #include <string>
 
+#include "dropout_math.hpp"
 #include "glu_math.hpp"
 #include "rope_math.hpp"
 #include "tokenizer.hpp"
@@ -592,17 +593,11 @@ __global__ __launch_bounds__(256) void glu_bwd_kernel(const unsigned short *gu, 
 }
 
 // ---- dropout (LoRA input dropout, peft LoraLayer) ---------------------------------------------------
-__device__ __forceinline__ unsigned mix32(unsigned long long seed, unsigned long long idx)
-{
-    unsigned long long z = seed + idx * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return (unsigned)((z ^ (z >> 31)) >> 32);
-}
+// mix32(seed, element index) >= p * 2^32 keeps the element: dropout_math.hpp (the attention kernels with dropout draw the same bits)
 __global__ __launch_bounds__(256) void dropout_kernel(const unsigned short *x, unsigned short *o, size_t n8, float p, float inv_keep,
                                                       unsigned long long seed)
 {
-    const unsigned thr = (unsigned)(p * 4294967296.0);
+    const unsigned thr = drop_threshold(p);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
         bf16x8 v = reinterpret_cast<const bf16x8 *>(x)[i];
 #pragma unroll

@@ -816,11 +816,17 @@ def _off(t, off):
     return C.c_void_p(t.data_ptr() + off * t.element_size())
 
 
-def attn_fwd(qkv, mask, B, S, Hq, Hkv, D, scale):
-    """Fused attention on a fused qkv buffer [B*S, Hq*D + 2*Hkv*D] (q | k | v).  Returns (o [B*S, Hq*D], lse)."""
+def attn_fwd(qkv, mask, B, S, Hq, Hkv, D, scale, drop=None):
+    """Fused attention on a fused qkv buffer [B*S, Hq*D + 2*Hkv*D] (q | k | v).  Returns (o [B*S, Hq*D], lse).
+    drop = (p, seed): inverted dropout on the probabilities inside the kernel (ecgb_attn_fwd_dropout: head_dim 64; the mask ops.dropout draws on a
+    contiguous [B*Hq, S, S] tensor from the same (p, seed)); lse is that of the undropped probabilities.  Hand the same `drop` to attn_bwd."""
     QKV = qkv.shape[1]
     o = torch.empty((B * S, Hq * D), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((B, Hq, S), dtype=torch.float32, device=qkv.device)
+    if drop is not None:
+        _lib.check(_L().ecgb_attn_fwd_dropout(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _off(qkv, Hq * D + Hkv * D), QKV, _p(mask),
+                                              _p(o), Hq * D, _p(lse), B, S, Hq, Hkv, D, float(scale), float(drop[0]), int(drop[1]), _st()))
+        return o, lse
     _lib.check(_L().ecgb_attn_fwd(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _off(qkv, Hq * D + Hkv * D), QKV, _p(mask),
                                   _p(o), Hq * D, _p(lse), B, S, Hq, Hkv, D, float(scale), _st()))
     return o, lse
@@ -898,15 +904,25 @@ def set_attn_bwd_rope_fusion(on=True):
     _fuse_rope_bwd = bool(on)
 
 
-def attn_bwd(qkv, mask, o, do, lse, B, S, Hq, Hkv, D, scale, rope=None):
+def attn_bwd(qkv, mask, o, do, lse, B, S, Hq, Hkv, D, scale, rope=None, drop=None):
     """Returns d_qkv with the same fused layout as qkv.  rope = (cos, sin) [B * S, D / 2] fp32: qkv holds the ROTATED q and k and d_qkv comes back as the
     gradient of the unrotated projection -- RoPE's backward in the attention kernels' own stores where they can (ecgb_attn_bwd_rope: head_dim 64, lean kernels),
-    otherwise as the separate pass it replaces (ecgb_rope, inverse); the same bits either way."""
+    otherwise as the separate pass it replaces (ecgb_rope, inverse); the same bits either way.
+    drop = (p, seed): the backward of attn_fwd(..., drop=drop) (ecgb_attn_bwd_dropout; o and lse are that forward's); RoPE's backward then always runs as the
+    separate pass."""
     QKV = qkv.shape[1]
     d_qkv = torch.empty_like(qkv)
     delta = torch.empty((B, Hq, S), dtype=torch.float32, device=qkv.device)
     nbytes = _L().ecgb_attn_bwd_scratch_bytes(B, S, Hq, Hkv, D)          # head_dim 256: partial dK / dV slabs (few key blocks) + the probabilities from the dK pass to the dV kernel; else 0
     scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=qkv.device) if nbytes else None
+    if drop is not None:
+        _lib.check(_L().ecgb_attn_bwd_dropout(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _off(qkv, Hq * D + Hkv * D), QKV, _p(mask),
+                                              _p(o), _p(_bf(do)), Hq * D, _p(lse), _p(delta), _off(d_qkv, 0), QKV, _off(d_qkv, Hq * D), QKV,
+                                              _off(d_qkv, Hq * D + Hkv * D), QKV, B, S, Hq, Hkv, D, float(scale), _p(scratch), nbytes,
+                                              float(drop[0]), int(drop[1]), _st()))
+        if rope is not None:
+            rope_(d_qkv, rope[0], rope[1], Hq + Hkv, D, QKV, inverse=True)
+        return d_qkv
     if rope is not None and _fuse_rope_bwd and D == 64:
         cos, sin = rope
         rc = _L().ecgb_attn_bwd_rope(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _off(qkv, Hq * D + Hkv * D), QKV, _p(mask),

@@ -11,10 +11,15 @@ What differs from the Llama block: LayerNorm with bias (ecgb_layernorm_fwd/bwd),
 no RoPE, multi-head attention (Hkv = Hq) on the same fused causal + left-padding attention kernels (head_dim 64 in every GPT-2 size).
 The loss: the reference does NOT upcast GPT-2's logits (modeling_gpt2.py:1300-1304 vs loss_utils.py:36): its bf16 run rounds the
 log-probabilities to bf16; the kernel here accumulates the same bf16 logits in fp32 (the difference is inside the 1e-2 loss tolerance).
-Dropout: embd_pdrop / resid_pdrop / attn_pdrop are applied in training mode (counter-based masks, replayed in the backward).  The
-fused attention kernels have no dropout on the probabilities, so a training step with attn_pdrop > 0 (GPT2Config's default 0.1)
-takes the materialised-scores attention (head-batched GEMMs + softmax kernel + dropout on P): slower, same semantics
-(modeling_gpt2.py:183-221); eval, generation and attn_pdrop = 0 run fused."""
+Dropout: embd_pdrop / resid_pdrop / attn_pdrop are applied in training mode (counter-based masks, replayed in the backward).  A
+training step with attn_pdrop > 0 (GPT2Config's default 0.1) has two forms of the attention (modeling_gpt2.py:183-221), which draw the
+same masks from the same seeds:
+  * `fused_attention_dropout = False` (default): the materialised-scores attention (head-batched GEMMs + softmax kernel + dropout on P);
+    every layer keeps the pair (P, dropped P), 2 B n_head S^2 bf16 values, for the backward;
+  * `fused_attention_dropout = True` (main.py --fused_attn_dropout): the fused kernels with the dropout inside (ops.attn_fwd / attn_bwd
+    with drop=(p, seed): the mask is evaluated again from (seed, element index) where it is needed); a layer keeps lse and (p, seed), and
+    no S x S tensor exists in HBM.
+Eval, generation and attn_pdrop = 0 run the fused kernels without dropout."""
 from __future__ import annotations
 
 import math
@@ -64,6 +69,7 @@ class GPT2Config:
 class HipGPT2LM(HipCausalLM):
     supports_optimizer_overlap = False   # its forward / backward carry no per-group waits: the optimizer step stays in-stream
     output_attentions_built = False      # its own _hidden_states: output_attentions raise NotImplementedError
+    fused_attention_dropout = False      # training with attn_pdrop > 0: True = dropout inside the fused attention kernels, False = the materialised scores
 
     def __init__(self, cfg: GPT2Config, device="cuda", seed: int = 0):
         nn.Module.__init__(self)
@@ -215,11 +221,14 @@ class HipGPT2LM(HipCausalLM):
         for i in range(c.n_layer):
             h1, mu1, rs1, x1 = ops.layernorm_fwd(x, self.ln1[i].data, self.ln1_b[i].data, eps, residual=delta)
             qkv = ops.bias_(ops.gemm_nt(h1, self.wqkv[i].data), self.bqkv[i].data)
-            if self.training and c.attn_pdrop > 0:                         # dropout on the probabilities: materialised scores
+            if self.training and c.attn_pdrop > 0:                         # dropout on the probabilities: inside the fused kernels, or materialised scores
                 self.drop_calls += 1
                 adrop = (c.attn_pdrop, self.drop_seed + 7919 * self.drop_calls + 4)
-                ao, lse = self._attn_materialised(qkv, mask, B, S, drop=adrop)
-                lse = (lse, adrop)
+                if self.fused_attention_dropout:
+                    ao, lse = ops.attn_fwd(qkv, mask, B, S, nh, nh, D, scale, drop=adrop)
+                else:
+                    ao, lse = self._attn_materialised(qkv, mask, B, S, drop=adrop)
+                lse = (lse, adrop)                                         # (lse, (p, seed)) fused, ((P, dropped P), (p, seed)) materialised
             else:
                 ao, lse = ops.attn_fwd(qkv, mask, B, S, nh, nh, D, scale)
             attn_delta = ops.bias_(ops.gemm_nt(ao, self.wo[i].data), self.bo[i].data)
@@ -278,8 +287,10 @@ class HipGPT2LM(HipCausalLM):
             self._vgrad(self.bo[i], ops.colsum(d_ad))
             self._wgrad(self.wo[i], d_ad, ao)
             d_ao = self._dx(d_ad, ("wo", i), self.wo[i])
-            if isinstance(lse, tuple):
+            if isinstance(lse, tuple) and isinstance(lse[0], tuple):
                 d_qkv = self._attn_materialised_bwd(qkv, d_ao, lse[0], B, S, drop=lse[1])
+            elif isinstance(lse, tuple):
+                d_qkv = ops.attn_bwd(qkv, mask, ao, d_ao, lse[0], B, S, nh, nh, D, scale, drop=lse[1])
             else:
                 d_qkv = ops.attn_bwd(qkv, mask, ao, d_ao, lse, B, S, nh, nh, D, scale)
             self._vgrad(self.bqkv[i], ops.colsum(d_qkv))

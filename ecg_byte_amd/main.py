@@ -69,6 +69,9 @@ def get_args(argv=None):
                         "batch-1 draws at the same seed (the distribution is the same)")
     p.add_argument("--device_sampler", action="store_true",
                    help="inference with a sampling checkpoint: draw the token on the device inside the replayed decode step (HipCausalLM.generate(device_sampler=True))")
+    p.add_argument("--fused_attn_dropout", action="store_true",
+                   help="GPT-2 training with attn_pdrop > 0: dropout on the attention probabilities inside the fused attention kernels (HipGPT2LM.fused_attention_dropout: "
+                        "no S x S tensor in HBM, the same masks) instead of the materialised-scores attention; other models ignore it")
     return p.parse_args(argv)
 
 
@@ -94,6 +97,8 @@ def build_model_and_tokenizer(args, vocab, device):
     llm.resize_token_embeddings(len(tokenizer))
     if args.peft:
         llm.enable_lora(r=16, alpha=32, dropout=0.05, seed=args.seed)
+    if getattr(args, "fused_attn_dropout", False) and hasattr(llm, "fused_attention_dropout"):
+        llm.fused_attention_dropout = True
     return LLM(llm, args), tokenizer
 
 

@@ -324,6 +324,26 @@ int ecgb_attn_bwd_rope(const void *q_dev, long long ldq, const void *k_dev, long
                        const float *lse_dev, float *delta_dev, void *dq_dev, long long lddq, void *dk_dev, long long lddk,
                        void *dv_dev, long long lddv, const float *rope_cos_dev, const float *rope_sin_dev, int batch, int seq, int n_q_heads,
                        int n_kv_heads, int head_dim, float scale, void *scratch_dev, size_t scratch_bytes, void *stream);
+/* ecgb_attn_fwd / ecgb_attn_bwd with inverted dropout on the attention probabilities (GPT-2's attn_dropout, modeling_gpt2.py:214) and still no S x S tensor in HBM:
+ * nothing of the mask is stored, both calls evaluate it from (p, seed).  Element (b, hq, query i, key j) is KEPT iff
+ *     mix32(seed, ((b * n_q_heads + hq) * seq + i) * seq + j) >= (unsigned)(p * 4294967296.0)          (64-bit index, p a float)
+ * -- the flat index and the rule ecgb_dropout_bf16 gives that element of a contiguous [batch * n_q_heads, seq, seq] tensor, so the materialised path
+ * (softmax kernel + ecgb_dropout_bf16) draws the same mask from the same (p, seed).  With Z = kept / (1 - p):
+ *     forward   o = (P o Z) V; row maxima, row sums and lse are those of the UNDROPPED probabilities (lse is what ecgb_attn_fwd writes for the same q, k)
+ *     backward  delta = rowsum(dO o O) with this forward's O; dP = (dO V^T) o Z; dS = P o (dP - delta) * scale; dV = (P o Z)^T dO; dQ, dK from dS as in ecgb_attn_bwd
+ * Masks (causal, left padding, rows without a visible key, grouped-query heads: the mask index uses the QUERY head) as in ecgb_attn_fwd / ecgb_attn_bwd; no atomics,
+ * the same bits every call.  Arguments: those of ecgb_attn_fwd / ecgb_attn_bwd with p and seed in front of the stream.
+ * p outside [0, 1) (NaN included): ECGB_ERR_INVALID.  p == 0: the call IS ecgb_attn_fwd / ecgb_attn_bwd (every head_dim they take, whichever kernel form is
+ * selected, the same bits).  p > 0: head_dim 64 only (ECGB_ERR_UNSUPPORTED otherwise), on the register-staged kernel family (mode 0 of ecgb_set_attn_fwd_staging,
+ * whatever mode is set).  All of this is decided before any launch. */
+int ecgb_attn_fwd_dropout(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
+                          const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
+                          int n_q_heads, int n_kv_heads, int head_dim, float scale, float p, uint64_t seed, void *stream);
+int ecgb_attn_bwd_dropout(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
+                          const float *attn_mask_dev, const void *o_dev, const void *do_dev, long long ldo, const float *lse_dev,
+                          float *delta_dev, void *dq_dev, long long lddq, void *dk_dev, long long lddk, void *dv_dev,
+                          long long lddv, int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim, float scale, void *scratch_dev, size_t scratch_bytes,
+                          float p, uint64_t seed, void *stream);
 
 /* One decode step of generate(): q [batch, n_q_heads*head_dim] against a KV cache whose rows (one per position) are
  * `ld` elements apart, `capacity` rows per batch entry, KV head g at + g*head_dim; the first kv_len rows are valid
