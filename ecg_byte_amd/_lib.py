@@ -244,6 +244,8 @@ def lib():
         "ecgb_attn_fwd_dropout": [vp, ll, vp, ll, vp, ll, vp, vp, ll, vp, ci, ci, ci, ci, ci, f32, f32, C.c_uint64, vp],
         "ecgb_attn_bwd_dropout": [vp, ll, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp, vp, ll, vp, ll, vp, ll, ci, ci, ci, ci, ci, f32, vp, sz, f32, C.c_uint64, vp],
         "ecgb_attn_bwd_rope": [vp, ll, vp, ll, vp, ll, vp, vp, vp, ll, vp, vp, vp, ll, vp, ll, vp, ll, vp, vp, ci, ci, ci, ci, ci, f32, vp, sz, vp],
+        "ecgb_attn_launch_plan": [ci, f32, vp, ll, vp, ll, vp, ll, vp, ll, vp, ll, vp, ll, vp, ll, vp, vp, ci, ci, ci, ci, ci, vp, sz,
+                                  C.POINTER(ci), C.POINTER(ci), C.POINTER(ll), C.c_char_p, ci],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)

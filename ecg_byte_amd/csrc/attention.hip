@@ -26,6 +26,10 @@
 //   backward  delta = rowsum(dO o O) with that O, dP = (dO V^T) o Z, dS = P o (dP - delta) scale, dV = (P o Z)^T dO.
 // The hash's argument is linear in the index, so its per-lane part (the row for forward / dQ, the key for dK / dV, and the lane half's 4 h offset inside a tile)
 // is formed once per kernel, the tile's part once per tile (uniform), and an element adds a constant: mix32_finish -- two 64-bit multiplies -- per score is what is left.
+#include <algorithm>
+#include <cstdio>
+#include <initializer_list>
+
 #include "attention_common.inc"
 #include "dropout_math.hpp"
 
@@ -1684,85 +1688,83 @@ LeanGeom lean_geom(int seq, int n_q_heads, int n_kv_heads, int batch)
     return {l2, (unsigned)((seq + rows - 1) / rows) * (unsigned)(n_q_heads >> l2) * (unsigned)batch};
 }
 
+// ---- dynamic LDS of each kernel family, in bytes (mask_lds_bytes, ring256_lds_bytes: attention_common.inc; the head_dim-256 backward: attention_d256.hip) ----
+// register-staged (attn_fwd_kernel<D>, attn_bwd_dq_kernel<D>, attn_bwd_dkv_kernel<D> / attn_bwd_dkv_pair_kernel<D>): tile buffers + the row's key mask / + the statistics
+long long fwd_lds_bytes(int D, int seq) { return 4 * 128 * D + mask_lds_bytes(seq); }
+long long dq_lds_bytes(int D, int seq) { return 3 * 128 * D + mask_lds_bytes(seq); }
+int dkv_lds_bytes(int D) { return 4 * 128 * D + 512; }
+// round-2 LDS-DMA, head_dim 64 (attn_fwd_kernel<64, true>, attn_bwd_dq_dma_kernel; attn_bwd_dkv_dma_kernel): rings of three
+long long dma_lds_bytes(int seq) { return 6 * 128 * 64 + mask_lds_bytes(seq); }
+int dkv_dma_lds_bytes() { return 3 * (2 * 128 * 64 + 1024); }
+// lean, head_dim 64 (attn_fwd_lean_kernel, attn_bwd_dq_lean_kernel: K / V ring, the key mask, 64 tile flags; attn_bwd_dkv_lean_kernel: Q / dO ring + a wave's statistics)
+long long lean_lds_bytes(int seq) { return 2 * kLeanRing * 128 * 64 + mask_lds_bytes(seq) + 256; }
+int dkv_lean_lds_bytes(int waves) { return kLeanRing * (2 * 128 * 64 + waves * 256); }
+// the most any form of the head dim that check_args() lets through may ask for at this length: the lean kernels at 64 (with their tile flags: every staging mode
+// takes the same lengths), the register-staged forward otherwise (the head_dim-256 ring is used only where it fits: plan_fwd / plan_bwd)
+long long attn_lds_max(int D, int seq) { return D == 64 ? std::max(lean_lds_bytes(seq), fwd_lds_bytes(D, seq)) : fwd_lds_bytes(D, seq); }
+
+// head_dim 256: may this pair of operands be staged by LDS-DMA?  16-byte aligned rows, and 64 rows + a row of 512 bytes inside the 32-bit per-lane offsets
+bool dma256_ok(const void *a, long long ld_a, const void *b, long long ld_b)
+{
+    return (ld_a & 7) == 0 && (ld_b & 7) == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0 && 64 * ld_a * 2 + 512 <= 0xFFFFFFFFll && 64 * ld_b * 2 + 512 <= 0xFFFFFFFFll;
+}
+
+int refuse(const char *who, const char *what, int code)
+{
+    ecgb::set_error(std::string(who) + ": " + what);
+    return code;
+}
+
 int check_args(const AttnArgs &A, int D, const char *who)
 {
-    if (A.B <= 0 || A.S <= 0 || A.Hq <= 0 || A.Hkv <= 0 || A.Hq % A.Hkv) {
-        ecgb::set_error(std::string(who) + ": bad shape");
-        return ECGB_ERR_INVALID;
-    }
-    if (D != 64 && D != 128 && D != 256) {
-        ecgb::set_error(std::string(who) + ": head_dim must be 64, 128 or 256");
-        return ECGB_ERR_UNSUPPORTED;
-    }
-    if (A.ldq % 8 || A.ldk % 8 || A.ldv % 8 || A.ldo % 8) {
-        ecgb::set_error(std::string(who) + ": row strides must be multiples of 8 elements");
-        return ECGB_ERR_UNSUPPORTED;
-    }
-    // tile buffers + the row's key mask in LDS; at head_dim 64 also the lean kernels' 64 tile flags (256 bytes), so that every form of the
-    // head dim takes the same lengths (without them 28 609..28 672 keys passed here and failed at the lean kernels' LDS attribute)
-    if ((D == 64 ? 6 : 4) * 128 * D + 4 * (((long long)A.S + 63) & ~63ll) + (D == 64 ? 256 : 0) > 160 * 1024) {
-        ecgb::set_error(std::string(who) + ": sequence too long for the key mask in LDS (head_dim 256: 8 192 keys, 128: 24 576, 64: 28 608)");
-        return ECGB_ERR_UNSUPPORTED;
-    }
+    if (A.B <= 0 || A.S <= 0 || A.Hq <= 0 || A.Hkv <= 0 || A.Hq % A.Hkv) return refuse(who, "bad shape", ECGB_ERR_INVALID);
+    if (D != 64 && D != 128 && D != 256) return refuse(who, "head_dim must be 64, 128 or 256", ECGB_ERR_UNSUPPORTED);
+    if (A.ldq % 8 || A.ldk % 8 || A.ldv % 8 || A.ldo % 8) return refuse(who, "row strides must be multiples of 8 elements", ECGB_ERR_UNSUPPORTED);
+    if (attn_lds_max(D, A.S) > kLdsMax)
+        return refuse(who, "sequence too long for the key mask in LDS (head_dim 256: 8 192 keys, 128: 24 576, 64: 28 608)", ECGB_ERR_UNSUPPORTED);
     return ECGB_OK;
 }
-
-// One kernel launch of the dispatch below: the dynamic-LDS attribute, then the launch; either failure is reported HERE with the kernel's name (a refused
-// attribute used to skip the launch silently and leave it to a later hipGetLastError -- which does not see it: the outputs stayed unwritten, status OK).
-template <typename Kern>
-int launch_attn(Kern kern, dim3 grid, dim3 block, int lds, void *stream, const AttnArgs &A, const char *what)
+// the entry points' first check
+int check_ptrs(const char *who, std::initializer_list<const void *> required)
 {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-        ecgb::set_error(std::string(what) + ": hipFuncSetAttribute(" + std::to_string(lds) + " bytes of dynamic LDS): " + hipGetErrorString(e));
-        return ECGB_ERR_HIP;
-    }
-    hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, A);
-    return launched(what);
+    for (const void *p : required)
+        if (!p) return refuse(who, "null pointer", ECGB_ERR_INVALID);
+    return ECGB_OK;
 }
-
-}  // namespace
-
-extern "C" int ecgb_attn_fwd(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
-                             const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
-                             int n_q_heads, int n_kv_heads, int head_dim, float scale, void *stream)
-{
-    AttnArgs A = {};
-    A.q = (const unsigned short *)q_dev; A.k = (const unsigned short *)k_dev; A.v = (const unsigned short *)v_dev;
-    A.ldq = ldq; A.ldk = ldk; A.ldv = ldv; A.mask = attn_mask_dev; A.o = (unsigned short *)o_dev; A.ldo = ldo; A.lse = lse_dev;
-    A.B = batch; A.S = seq; A.Hq = n_q_heads; A.Hkv = n_kv_heads; A.scale = scale;
-    int rc = check_args(A, head_dim, "ecgb_attn_fwd");
-    if (rc) return rc;
-    const dim3 grid((unsigned)((seq + 127) / 128) * (unsigned)n_q_heads * (unsigned)batch);   // 1-D: map_block() deals blocks to XCDs
-    if (head_dim == 64) {
-        const int lds = 6 * 128 * 64 + 4 * ((seq + 63) & ~63);
-        if ((g_attn_dma & 3) == 2 && !(g_attn_dma & 0x100)) {
-            const int ldl = 2 * kLeanRing * 128 * 64 + 4 * ((seq + 63) & ~63) + 256;   // K / V ring, the row's key mask, 64 tile flags
-            const LeanGeom lg = lean_geom(seq, n_q_heads, n_kv_heads, batch);
-            A.lean_hw_log2 = lg.hw_log2;
-            auto kf = g_lean_waves == 8 ? attn_fwd_lean_kernel<8> : attn_fwd_lean_kernel<4>;
-            return launch_attn(kf, dim3(lg.grid), dim3(g_lean_waves * 64), ldl, stream, A, "attn_fwd_lean_kernel");
-        }
-        if (g_attn_dma & 3) return launch_attn(attn_fwd_kernel<64, true>, grid, dim3(256), lds, stream, A, "attn_fwd_kernel<64, dma>");
-        return launch_attn(attn_fwd_kernel<64>, grid, dim3(256), 4 * 128 * 64 + 4 * ((seq + 63) & ~63), stream, A, "attn_fwd_kernel<64>");
-    }
-    if (head_dim == 128) return launch_attn(attn_fwd_kernel<128>, grid, dim3(256), 4 * 128 * 128 + 4 * ((seq + 63) & ~63), stream, A, "attn_fwd_kernel<128>");
-    // head_dim 256: LDS-DMA staging (round 4) where its two-stage ring, the key mask and the tile flags fit the CU's 160 KB and the per-lane DMA offsets 32 bits; mode 0 of
-    // ecgb_set_attn_fwd_staging keeps the register-staged kernel (A/B, tests)
-    const long long lds256 = 4ll * 64 * 512 + 4ll * ((seq + 63) & ~63) + 256;
-    if ((g_attn_dma & 3) && lds256 <= 160 * 1024 && (ldk & 7) == 0 && (ldv & 7) == 0 && (((uintptr_t)k_dev | (uintptr_t)v_dev) & 15) == 0 && 64 * ldk * 2 + 512 <= 0xFFFFFFFFll && 64 * ldv * 2 + 512 <= 0xFFFFFFFFll)
-        return launch_attn(attn_fwd_d256_kernel, grid, dim3(256), (int)lds256, stream, A, "attn_fwd_d256_kernel");
-    return launch_attn(attn_fwd_kernel<256>, grid, dim3(256), 4 * 128 * 256 + 4 * ((seq + 63) & ~63), stream, A, "attn_fwd_kernel<256>");
-}
-
-namespace {
-// what ecgb_attn_fwd_dropout / ecgb_attn_bwd_dropout ask of (p, head_dim) before anything is launched; 1: p == 0, the plain entry point serves the call
+// what ecgb_attn_fwd_dropout / ecgb_attn_bwd_dropout ask of (p, head_dim); p == 0 is the plain call
 int check_drop(float p, int head_dim, const char *who)
 {
-    if (!(p >= 0.f && p < 1.f)) { ecgb::set_error(std::string(who) + ": 0 <= p < 1 required"); return ECGB_ERR_INVALID; }
-    if (p == 0.f) return 1;
-    if (head_dim != 64) { ecgb::set_error(std::string(who) + ": dropout on the probabilities is built for head_dim 64 only"); return ECGB_ERR_UNSUPPORTED; }
+    if (!(p >= 0.f && p < 1.f)) return refuse(who, "0 <= p < 1 required", ECGB_ERR_INVALID);
+    if (p > 0.f && head_dim != 64) return refuse(who, "dropout on the probabilities is built for head_dim 64 only", ECGB_ERR_UNSUPPORTED);
     return ECGB_OK;
+}
+// what ecgb_attn_bwd_rope asks: store_accT_rope_inv is in the lean backward kernels only and stores 16 bytes at a time
+int check_rope(const void *dq, long long lddq, const void *dk, long long lddk, const void *rope_cos, const void *rope_sin, int head_dim, const char *who)
+{
+    if (!rope_cos || !rope_sin) return refuse(who, "NULL table", ECGB_ERR_INVALID);
+    if (head_dim != 64 || (g_attn_dma & 0x703) != 2 || (lddq & 7) || (lddk & 7) || (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)rope_cos | (uintptr_t)rope_sin) & 15))
+        return refuse(who, "head_dim 64 on the lean kernels with 16-byte aligned gradient rows only", ECGB_ERR_UNSUPPORTED);
+    return ECGB_OK;
+}
+
+// ---- the argument block: the forward's fields, what the backward adds, dropout, what a plan decides ----
+AttnArgs attn_args(const void *q, long long ldq, const void *k, long long ldk, const void *v, long long ldv, const float *mask, const void *o, long long ldo,
+                   const float *lse, int batch, int seq, int n_q_heads, int n_kv_heads, float scale)
+{
+    AttnArgs A = {};
+    A.q = (const unsigned short *)q; A.k = (const unsigned short *)k; A.v = (const unsigned short *)v;
+    A.ldq = ldq; A.ldk = ldk; A.ldv = ldv; A.mask = mask; A.o = (unsigned short *)const_cast<void *>(o); A.ldo = ldo; A.lse = const_cast<float *>(lse);
+    A.B = batch; A.S = seq; A.Hq = n_q_heads; A.Hkv = n_kv_heads; A.scale = scale;
+    return A;
+}
+void attn_args_bwd(AttnArgs &A, const void *d_o, float *delta, void *dq, long long lddq, void *dk, long long lddk, void *dv, long long lddv, void *scratch,
+                   const float *rope_cos, const float *rope_sin)
+{
+    A.d_o = (const unsigned short *)d_o; A.delta = delta;
+    A.dq = (unsigned short *)dq; A.dk = (unsigned short *)dk; A.dv = (unsigned short *)dv;
+    A.lddq = lddq; A.lddk = lddk; A.lddv = lddv;
+    A.slab = (float *)scratch;
+    A.rope_cos = rope_cos; A.rope_sin = rope_sin;
 }
 void set_drop(AttnArgs &A, float p, uint64_t seed)
 {
@@ -1770,27 +1772,18 @@ void set_drop(AttnArgs &A, float p, uint64_t seed)
     A.drop_thr = drop_threshold(p);
     A.drop_inv = 1.0f / (1.0f - p);                          // (as ecgb_dropout_bf16 forms it)
 }
-}  // namespace
 
-extern "C" int ecgb_attn_fwd_dropout(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
-                                     const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
-                                     int n_q_heads, int n_kv_heads, int head_dim, float scale, float p, uint64_t seed, void *stream)
-{
-    int rc = check_drop(p, head_dim, "ecgb_attn_fwd_dropout");
-    if (rc == 1) return ecgb_attn_fwd(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, ldo, lse_dev, batch, seq, n_q_heads, n_kv_heads, head_dim, scale, stream);
-    if (rc) return rc;
-    AttnArgs A = {};
-    A.q = (const unsigned short *)q_dev; A.k = (const unsigned short *)k_dev; A.v = (const unsigned short *)v_dev;
-    A.ldq = ldq; A.ldk = ldk; A.ldv = ldv; A.mask = attn_mask_dev; A.o = (unsigned short *)o_dev; A.ldo = ldo; A.lse = lse_dev;
-    A.B = batch; A.S = seq; A.Hq = n_q_heads; A.Hkv = n_kv_heads; A.scale = scale;
-    set_drop(A, p, seed);
-    rc = check_args(A, head_dim, "ecgb_attn_fwd_dropout");
-    if (rc) return rc;
-    const dim3 grid((unsigned)((seq + 127) / 128) * (unsigned)n_q_heads * (unsigned)batch);
-    return launch_attn(attn_fwd_kernel<64, false, true>, grid, dim3(256), 4 * 128 * 64 + 4 * ((seq + 63) & ~63), stream, A, "attn_fwd_kernel<64, dropout>");
-}
+// ---- the dispatch: which kernels a call launches, in order, and what it sets in the argument block.  No HIP call: ecgb_attn_launch_plan reads it without a device ----
+struct AttnPlan {
+    AttnLaunch launch[4];
+    int n = 0;
+    int lean_hw_log2 = 0, head_splits = 0;
+    unsigned short *pbuf = nullptr;
+    void add(const AttnLaunch &l) { launch[n++] = l; }
+    void add(AttnKern kern, const char *name, unsigned grid, unsigned block, long long lds) { launch[n++] = {kern, name, grid, block, (int)lds}; }
+};
+void set_plan(AttnArgs &A, const AttnPlan &P) { A.lean_hw_log2 = P.lean_hw_log2; A.head_splits = P.head_splits; A.pbuf = P.pbuf; }
 
-namespace {
 // head_dim 256 with few (batch, KV head, key block) workgroups: the causal key blocks differ 16-fold in work and one launch of <= 256
 // workgroups takes as long as its heaviest one (key block 0).  Splitting a group's query heads over 2..4 workgroups gives the scheduler
 // pieces to balance with (heaviest first); the price is fp32 partial slabs and a small ordered reduction.
@@ -1803,110 +1796,159 @@ int dkv_head_splits(int batch, int seq, int n_q_heads, int n_kv_heads, int head_
     while (wgs * hs < 1024 && hs * 2 <= 4 && G % (hs * 2) == 0) hs *= 2;
     return hs;
 }
-}  // namespace
-
-namespace {
+size_t dkv_slab_bytes(int hs, int batch, int seq, int n_kv_heads, int head_dim)
+{
+    return hs > 1 ? (size_t)2 * hs * batch * seq * n_kv_heads * head_dim * sizeof(float) : 0;
+}
 // head_dim 256 (round 6): room for the probabilities the dK pass hands to the dV kernel (AttnArgs::pbuf), bf16 over whole 128-key x 64-query tiles
 size_t attn_bwd_p_bytes(int batch, int seq, int n_q_heads, int head_dim)
 {
     if (head_dim != 256 || !g_attn_d256_pass_p) return 0;
     return (size_t)batch * n_q_heads * ((seq + 127) / 128) * ((seq + 63) / 64) * (128 * 64 * 2);
 }
+
+// head_dim 64 by ecgb_set_attn_fwd_staging (the lean kernels, | 0x100: the round-2 LDS-DMA kernel, 0: register-staged) -- with dropout always register-staged;
+// head_dim 256: LDS-DMA staging (round 4) where its ring fits the CU's LDS and dma256_ok(k, v), mode 0 keeps the register-staged kernel (A/B, tests)
+int plan_fwd(const AttnArgs &A, int D, bool drop, const char *who, AttnPlan &P)
+{
+    const int rc = check_args(A, D, who);
+    if (rc) return rc;
+    const int seq = A.S, mode = drop ? 0 : g_attn_dma & 3;
+    const unsigned grid = (unsigned)((seq + 127) / 128) * (unsigned)A.Hq * (unsigned)A.B;       // 1-D: map_block() deals blocks to XCDs
+    if (D == 64 && mode == 2 && !(g_attn_dma & 0x100)) {
+        const LeanGeom lg = lean_geom(seq, A.Hq, A.Hkv, A.B);
+        P.lean_hw_log2 = lg.hw_log2;
+        P.add(g_lean_waves == 8 ? attn_fwd_lean_kernel<8> : attn_fwd_lean_kernel<4>, "attn_fwd_lean_kernel", lg.grid, g_lean_waves * 64, lean_lds_bytes(seq));
+    } else if (D == 64 && mode) {
+        P.add(attn_fwd_kernel<64, true>, "attn_fwd_kernel<64, dma>", grid, 256, dma_lds_bytes(seq));
+    } else if (D == 64 && !drop) {
+        P.add(attn_fwd_kernel<64>, "attn_fwd_kernel<64>", grid, 256, fwd_lds_bytes(64, seq));
+    } else if (D == 128) {
+        P.add(attn_fwd_kernel<128>, "attn_fwd_kernel<128>", grid, 256, fwd_lds_bytes(128, seq));
+    } else if (D == 256 && mode && ring256_lds_bytes(seq) <= kLdsMax && dma256_ok(A.k, A.ldk, A.v, A.ldv)) {
+        P.add(attn_fwd_d256_kernel, "attn_fwd_d256_kernel", grid, 256, ring256_lds_bytes(seq));
+    } else if (D == 256) {
+        P.add(attn_fwd_kernel<256>, "attn_fwd_kernel<256>", grid, 256, fwd_lds_bytes(256, seq));
+    } else {                                                                                    // dropout (head_dim 64: check_drop)
+        P.add(attn_fwd_kernel<64, false, true>, "attn_fwd_kernel<64, dropout>", grid, 256, fwd_lds_bytes(64, seq));
+    }
+    return ECGB_OK;
+}
+
+// dQ, then dK / dV (head_dim 256: the pair kernel, or with the whole of ecgb_attn_bwd_scratch_bytes() the dK pass that hands its probabilities to a dV kernel), then
+// the reduction of the head-split slabs.  head_dim 64: | 0x200 / 0x400 keep dQ / dK-dV alone on the round-2 kernels; with dropout the register-staged DROP forms
+int plan_bwd(const AttnArgs &A, int D, bool drop, const void *scratch, size_t scratch_bytes, const char *who, AttnPlan &P)
+{
+    const int rc = check_args(A, D, who);
+    if (rc) return rc;
+    if (A.lddq % 4 || A.lddk % 4 || A.lddv % 4) return refuse(who, "gradient row strides must be multiples of 4", ECGB_ERR_UNSUPPORTED);
+    const int seq = A.S, mode = drop ? 0 : g_attn_dma & 3;
+    P.head_splits = dkv_head_splits(A.B, seq, A.Hq, A.Hkv, D);
+    const unsigned hs = (unsigned)P.head_splits;
+    const size_t slab_bytes = dkv_slab_bytes(P.head_splits, A.B, seq, A.Hkv, D);
+    const bool scratch_ok = scratch && ((uintptr_t)scratch & 15) == 0;
+    if (hs > 1 && (!scratch_ok || scratch_bytes < slab_bytes))
+        return refuse(who, "scratch for the partial dK / dV slabs (16-byte aligned; ecgb_attn_bwd_scratch_bytes() says how much) required for this shape", ECGB_ERR_INVALID);
+    const unsigned nblk = (unsigned)((seq + 127) / 128);
+    const unsigned gq = nblk * (unsigned)A.Hq * (unsigned)A.B, gk = nblk * (unsigned)A.Hkv * (unsigned)A.B;       // 1-D: map_block() deals blocks to XCDs
+    if (D == 64 && !drop) {
+        const bool lq_lean = mode == 2 && !(g_attn_dma & 0x200), lk_lean = mode == 2 && !(g_attn_dma & 0x400);
+        const LeanGeom lg = lean_geom(seq, A.Hq, A.Hkv, A.B);
+        if (mode) P.lean_hw_log2 = lg.hw_log2;
+        if (lq_lean) P.add(g_lean_waves == 8 ? attn_bwd_dq_lean_kernel<8> : attn_bwd_dq_lean_kernel<4>, "attn_bwd_dq_lean_kernel", lg.grid, g_lean_waves * 64, lean_lds_bytes(seq));
+        else if (mode) P.add(attn_bwd_dq_dma_kernel, "attn_bwd_dq_dma_kernel", gq, 256, dma_lds_bytes(seq));
+        else P.add(attn_bwd_dq_kernel<64>, "attn_bwd_dq_kernel<64>", gq, 256, dq_lds_bytes(64, seq));
+        const unsigned gkl = (unsigned)(((seq + g_lean_waves * 32 - 1) / (g_lean_waves * 32) + 1) / 2) * (unsigned)A.Hkv * (unsigned)A.B;   // key blocks in pairs (j, n - 1 - j)
+        if (lk_lean) P.add(g_lean_waves == 8 ? attn_bwd_dkv_lean_kernel<8> : attn_bwd_dkv_lean_kernel<4>, "attn_bwd_dkv_lean_kernel", gkl, g_lean_waves * 64, dkv_lean_lds_bytes(g_lean_waves));
+        else if (mode) P.add(attn_bwd_dkv_dma_kernel, "attn_bwd_dkv_dma_kernel", gk, 256, dkv_dma_lds_bytes());
+        else P.add(attn_bwd_dkv_kernel<64, 1, 0>, "attn_bwd_dkv_kernel<64>", gk, 256, dkv_lds_bytes(64));
+    } else if (D == 128) {
+        P.add(attn_bwd_dq_kernel<128>, "attn_bwd_dq_kernel<128>", gq, 256, dq_lds_bytes(128, seq));
+        P.add(attn_bwd_dkv_kernel<128, 1, 0>, "attn_bwd_dkv_kernel<128>", gk, 256, dkv_lds_bytes(128));
+    } else if (D == 256) {
+        if (mode && ring256_lds_bytes(seq) <= kLdsMax && dma256_ok(A.k, A.ldk, A.v, A.ldv)) P.add(ecgb_attn::bwd_dq_d256(gq, seq));
+        else P.add(attn_bwd_dq_kernel<256>, "attn_bwd_dq_kernel<256>", gq, 256, dq_lds_bytes(256, seq));
+        const size_t p_bytes = attn_bwd_p_bytes(A.B, seq, A.Hq, D);
+        if (!(mode && dma256_ok(A.q, A.ldq, A.d_o, A.ldo))) {
+            P.add(attn_bwd_dkv_pair_kernel<256>, "attn_bwd_dkv_pair_kernel<256>", gk * 2 * hs, 256, dkv_lds_bytes(256));
+        } else if (p_bytes > 0 && scratch_ok && scratch_bytes >= slab_bytes + p_bytes) {
+            P.pbuf = reinterpret_cast<unsigned short *>(reinterpret_cast<unsigned char *>(const_cast<void *>(scratch)) + slab_bytes);
+            P.add(ecgb_attn::bwd_dk_d256(gk * hs));
+            P.add(ecgb_attn::bwd_dv_d256(gk * hs));
+        } else {
+            P.add(ecgb_attn::bwd_dkv_pair_d256(gk * 2 * hs));
+        }
+        if (hs > 1) P.add(attn_dkv_reduce_kernel<256>, "attn_dkv_reduce_kernel<256>", 2048, 256, 0);
+    } else {                                                                                    // dropout (head_dim 64: check_drop)
+        P.add(attn_bwd_dq_kernel<64, true>, "attn_bwd_dq_kernel<64, dropout>", gq, 256, dq_lds_bytes(64, seq));
+        P.add(attn_bwd_dkv_kernel<64, 1, 0, true>, "attn_bwd_dkv_kernel<64, dropout>", gk, 256, dkv_lds_bytes(64));
+    }
+    return ECGB_OK;
+}
+
+int run_plan(AttnArgs &A, const AttnPlan &P, void *stream)
+{
+    set_plan(A, P);
+    for (int i = 0; i < P.n; ++i) {
+        const AttnLaunch &l = P.launch[i];
+        const int rc = launch_attn(l.kern, l.name, l.grid, l.block, l.lds, stream, A);
+        if (rc) return rc;
+    }
+    return ECGB_OK;
+}
+
+// the one forward body and the one backward body; p > 0: dropout on the probabilities from (p, seed)
+int attn_fwd_impl(const char *who, const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
+                  const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
+                  int n_q_heads, int n_kv_heads, int head_dim, float scale, float p, uint64_t seed, void *stream)
+{
+    AttnArgs A = attn_args(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, ldo, lse_dev, batch, seq, n_q_heads, n_kv_heads, scale);
+    if (p > 0.f) set_drop(A, p, seed);
+    AttnPlan P;
+    const int rc = plan_fwd(A, head_dim, p > 0.f, who, P);
+    return rc ? rc : run_plan(A, P, stream);
+}
+int attn_bwd_impl(const char *who, const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
+                  const float *attn_mask_dev, const void *o_dev, const void *do_dev, long long ldo,
+                  const float *lse_dev, float *delta_dev, void *dq_dev, long long lddq, void *dk_dev, long long lddk,
+                  void *dv_dev, long long lddv, int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                  float scale, void *scratch_dev, size_t scratch_bytes, void *stream, const float *rope_cos, const float *rope_sin, float p, uint64_t seed)
+{
+    AttnArgs A = attn_args(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, ldo, lse_dev, batch, seq, n_q_heads, n_kv_heads, scale);
+    attn_args_bwd(A, do_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv, scratch_dev, rope_cos, rope_sin);
+    if (p > 0.f) set_drop(A, p, seed);
+    AttnPlan P;
+    const int rc = plan_bwd(A, head_dim, p > 0.f, scratch_dev, scratch_bytes, who, P);
+    return rc ? rc : run_plan(A, P, stream);
+}
+
 }  // namespace
+
+extern "C" int ecgb_attn_fwd(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
+                             const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
+                             int n_q_heads, int n_kv_heads, int head_dim, float scale, void *stream)
+{
+    const char *who = "ecgb_attn_fwd";
+    if (int rc = check_ptrs(who, {q_dev, k_dev, v_dev, attn_mask_dev, o_dev, lse_dev})) return rc;
+    return attn_fwd_impl(who, q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, ldo, lse_dev, batch, seq, n_q_heads, n_kv_heads, head_dim, scale, 0.f, 0, stream);
+}
+
+extern "C" int ecgb_attn_fwd_dropout(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
+                                     const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
+                                     int n_q_heads, int n_kv_heads, int head_dim, float scale, float p, uint64_t seed, void *stream)
+{
+    const char *who = "ecgb_attn_fwd_dropout";
+    if (int rc = check_ptrs(who, {q_dev, k_dev, v_dev, attn_mask_dev, o_dev, lse_dev})) return rc;
+    if (int rc = check_drop(p, head_dim, who)) return rc;
+    return attn_fwd_impl(who, q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, ldo, lse_dev, batch, seq, n_q_heads, n_kv_heads, head_dim, scale, p, seed, stream);
+}
 
 extern "C" size_t ecgb_attn_bwd_scratch_bytes(int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim)
 {
     if (batch <= 0 || seq <= 0 || n_q_heads <= 0 || n_kv_heads <= 0 || n_q_heads % n_kv_heads) return 0;
     const int hs = dkv_head_splits(batch, seq, n_q_heads, n_kv_heads, head_dim);
-    const size_t slabs = hs > 1 ? (size_t)2 * hs * batch * seq * n_kv_heads * head_dim * sizeof(float) : 0;
-    return slabs + attn_bwd_p_bytes(batch, seq, n_q_heads, head_dim);
+    return dkv_slab_bytes(hs, batch, seq, n_kv_heads, head_dim) + attn_bwd_p_bytes(batch, seq, n_q_heads, head_dim);
 }
-
-namespace {
-int attn_bwd_impl(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
-                  const float *attn_mask_dev, const void *o_dev, const void *do_dev, long long ldo,
-                  const float *lse_dev, float *delta_dev, void *dq_dev, long long lddq, void *dk_dev, long long lddk,
-                  void *dv_dev, long long lddv, int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim,
-                  float scale, void *scratch_dev, size_t scratch_bytes, void *stream, const float *rope_cos, const float *rope_sin)
-{
-    AttnArgs A = {};
-    A.rope_cos = rope_cos; A.rope_sin = rope_sin;
-    A.q = (const unsigned short *)q_dev; A.k = (const unsigned short *)k_dev; A.v = (const unsigned short *)v_dev;
-    A.ldq = ldq; A.ldk = ldk; A.ldv = ldv; A.mask = attn_mask_dev; A.o = (unsigned short *)const_cast<void *>(o_dev); A.ldo = ldo;
-    A.lse = const_cast<float *>(lse_dev); A.d_o = (const unsigned short *)do_dev; A.delta = delta_dev;
-    A.dq = (unsigned short *)dq_dev; A.dk = (unsigned short *)dk_dev; A.dv = (unsigned short *)dv_dev;
-    A.lddq = lddq; A.lddk = lddk; A.lddv = lddv;
-    A.B = batch; A.S = seq; A.Hq = n_q_heads; A.Hkv = n_kv_heads; A.scale = scale;
-    int rc = check_args(A, head_dim, "ecgb_attn_bwd");
-    if (rc) return rc;
-    if (lddq % 4 || lddk % 4 || lddv % 4) { ecgb::set_error("ecgb_attn_bwd: gradient row strides must be multiples of 4"); return ECGB_ERR_UNSUPPORTED; }
-    A.head_splits = dkv_head_splits(batch, seq, n_q_heads, n_kv_heads, head_dim);
-    A.slab = (float *)scratch_dev;
-    const size_t slab_bytes = A.head_splits > 1 ? (size_t)2 * A.head_splits * batch * seq * n_kv_heads * head_dim * sizeof(float) : 0;
-    if (A.head_splits > 1 && (!scratch_dev || ((uintptr_t)scratch_dev & 15) || scratch_bytes < slab_bytes)) {
-        ecgb::set_error("ecgb_attn_bwd: scratch for the partial dK / dV slabs (16-byte aligned; ecgb_attn_bwd_scratch_bytes() says how much) required for this shape");
-        return ECGB_ERR_INVALID;
-    }
-    // (head_dim 256: with the whole of ecgb_attn_bwd_scratch_bytes() the dK pass hands its probabilities to the dV kernel; with the slabs' share alone the dV pass forms them again)
-    const size_t p_bytes = attn_bwd_p_bytes(batch, seq, n_q_heads, head_dim);
-    const bool pass_p = g_attn_d256_pass_p && p_bytes > 0 && scratch_dev && ((uintptr_t)scratch_dev & 15) == 0 && scratch_bytes >= slab_bytes + p_bytes;
-    const unsigned nblk = (unsigned)((seq + 127) / 128);
-    const dim3 gq(nblk * (unsigned)n_q_heads * (unsigned)batch);          // 1-D: map_block() deals blocks to XCDs
-    const unsigned gk = nblk * (unsigned)n_kv_heads * (unsigned)batch;
-    auto dq_generic = [&](auto kern, int D_, const char *what) { return launch_attn(kern, gq, dim3(256), 3 * 128 * D_ + 4 * ((seq + 63) & ~63), stream, A, what); };
-    if (head_dim == 64) {
-        const bool lean = (g_attn_dma & 3) == 2;
-        if (g_attn_dma & 3) {
-            const bool lq_lean = lean && !(g_attn_dma & 0x200);
-            const int lq = (lq_lean ? 2 * kLeanRing : 6) * 128 * 64 + 4 * ((seq + 63) & ~63) + (lq_lean ? 256 : 0);
-            const LeanGeom lg = lean_geom(seq, n_q_heads, n_kv_heads, batch);
-            A.lean_hw_log2 = lg.hw_log2;
-            auto kq = !lq_lean ? attn_bwd_dq_dma_kernel : g_lean_waves == 8 ? attn_bwd_dq_lean_kernel<8> : attn_bwd_dq_lean_kernel<4>;
-            rc = launch_attn(kq, lq_lean ? dim3(lg.grid) : gq, dim3(lq_lean ? g_lean_waves * 64 : 256), lq, stream, A, lq_lean ? "attn_bwd_dq_lean_kernel" : "attn_bwd_dq_dma_kernel");
-        } else {
-            rc = dq_generic(attn_bwd_dq_kernel<64>, 64, "attn_bwd_dq_kernel<64>");
-        }
-        if (rc) return rc;
-        if (g_attn_dma & 3) {
-            const bool lk_lean = lean && !(g_attn_dma & 0x400);
-            const int lk = lk_lean ? kLeanRing * (2 * 128 * 64 + g_lean_waves * 256) : 3 * (2 * 128 * 64 + 1024);
-            auto kk = !lk_lean ? attn_bwd_dkv_dma_kernel : g_lean_waves == 8 ? attn_bwd_dkv_lean_kernel<8> : attn_bwd_dkv_lean_kernel<4>;
-            const unsigned gkl = (unsigned)(((seq + g_lean_waves * 32 - 1) / (g_lean_waves * 32) + 1) / 2) * (unsigned)n_kv_heads * (unsigned)batch;   // key blocks in pairs (j, n - 1 - j)
-            return launch_attn(kk, dim3(lk_lean ? gkl : gk), dim3(lk_lean ? g_lean_waves * 64 : 256), lk, stream, A, lk_lean ? "attn_bwd_dkv_lean_kernel" : "attn_bwd_dkv_dma_kernel");
-        }
-        return launch_attn(attn_bwd_dkv_kernel<64, 1, 0>, dim3(gk), dim3(256), 4 * 128 * 64 + 512, stream, A, "attn_bwd_dkv_kernel<64>");
-    }
-    if (head_dim == 128) {
-        rc = dq_generic(attn_bwd_dq_kernel<128>, 128, "attn_bwd_dq_kernel<128>");
-        if (rc) return rc;
-        return launch_attn(attn_bwd_dkv_kernel<128, 1, 0>, dim3(gk), dim3(256), 4 * 128 * 128 + 512, stream, A, "attn_bwd_dkv_kernel<128>");
-    }
-    // head_dim 256: LDS-DMA staging where the two-stage ring fits (see ecgb_attn_fwd); mode 0 of ecgb_set_attn_fwd_staging keeps the register-staged kernels
-    const long long lds256 = 4ll * 64 * 512 + 4ll * ((seq + 63) & ~63) + 256;
-    const bool dma256 = (g_attn_dma & 3) && lds256 <= 160 * 1024 && (ldk & 7) == 0 && (ldv & 7) == 0 && (((uintptr_t)k_dev | (uintptr_t)v_dev) & 15) == 0 &&
-                        64 * ldk * 2 + 512 <= 0xFFFFFFFFll && 64 * ldv * 2 + 512 <= 0xFFFFFFFFll;
-    if (dma256) rc = ecgb_attn::launch_bwd_dq_d256(A, gq.x, seq, stream);
-    else rc = dq_generic(attn_bwd_dq_kernel<256>, 256, "attn_bwd_dq_kernel<256>");
-    if (rc) return rc;
-    if ((g_attn_dma & 3) && (ldq & 7) == 0 && (ldo & 7) == 0 && (((uintptr_t)q_dev | (uintptr_t)do_dev) & 15) == 0 && 64 * ldq * 2 + 512 <= 0xFFFFFFFFll && 64 * ldo * 2 + 512 <= 0xFFFFFFFFll)
-    {
-        if (pass_p) {
-            A.pbuf = reinterpret_cast<unsigned short *>(reinterpret_cast<unsigned char *>(scratch_dev) + slab_bytes);
-            rc = ecgb_attn::launch_bwd_dk_then_dv_d256(A, gk * (unsigned)A.head_splits, stream);
-        } else {
-            rc = ecgb_attn::launch_bwd_dkv_pair_d256(A, gk * 2 * (unsigned)A.head_splits, stream);
-        }
-    }
-    else
-        rc = launch_attn(attn_bwd_dkv_pair_kernel<256>, dim3(gk * 2 * (unsigned)A.head_splits), dim3(256), 4 * 128 * 256 + 512, stream, A, "attn_bwd_dkv_pair_kernel<256>");
-    if (rc) return rc;
-    if (A.head_splits > 1) {
-        hipLaunchKernelGGL(attn_dkv_reduce_kernel<256>, dim3(2048), dim3(256), 0, (hipStream_t)stream, A);
-        return launched("attn_dkv_reduce_kernel<256>");
-    }
-    return ECGB_OK;
-}
-}  // namespace
 
 extern "C" int ecgb_attn_bwd(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
                              const float *attn_mask_dev, const void *o_dev, const void *do_dev, long long ldo,
@@ -1914,8 +1956,10 @@ extern "C" int ecgb_attn_bwd(const void *q_dev, long long ldq, const void *k_dev
                              void *dv_dev, long long lddv, int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim,
                              float scale, void *scratch_dev, size_t scratch_bytes, void *stream)
 {
-    return attn_bwd_impl(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, do_dev, ldo, lse_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv,
-                         batch, seq, n_q_heads, n_kv_heads, head_dim, scale, scratch_dev, scratch_bytes, stream, nullptr, nullptr);
+    const char *who = "ecgb_attn_bwd";
+    if (int rc = check_ptrs(who, {q_dev, k_dev, v_dev, attn_mask_dev, o_dev, lse_dev, do_dev, delta_dev, dq_dev, dk_dev, dv_dev})) return rc;
+    return attn_bwd_impl(who, q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, do_dev, ldo, lse_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv,
+                         batch, seq, n_q_heads, n_kv_heads, head_dim, scale, scratch_dev, scratch_bytes, stream, nullptr, nullptr, 0.f, 0);
 }
 
 // the backward of ecgb_attn_fwd_dropout (o_dev and lse_dev are that forward's): two launches of the register-staged kernels' DROP forms; the scratch is not used
@@ -1925,28 +1969,11 @@ extern "C" int ecgb_attn_bwd_dropout(const void *q_dev, long long ldq, const voi
                                      void *dv_dev, long long lddv, int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim,
                                      float scale, void *scratch_dev, size_t scratch_bytes, float p, uint64_t seed, void *stream)
 {
-    int rc = check_drop(p, head_dim, "ecgb_attn_bwd_dropout");
-    if (rc == 1) return ecgb_attn_bwd(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, do_dev, ldo, lse_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv,
-                                      batch, seq, n_q_heads, n_kv_heads, head_dim, scale, scratch_dev, scratch_bytes, stream);
-    if (rc) return rc;
-    AttnArgs A = {};
-    A.q = (const unsigned short *)q_dev; A.k = (const unsigned short *)k_dev; A.v = (const unsigned short *)v_dev;
-    A.ldq = ldq; A.ldk = ldk; A.ldv = ldv; A.mask = attn_mask_dev; A.o = (unsigned short *)const_cast<void *>(o_dev); A.ldo = ldo;
-    A.lse = const_cast<float *>(lse_dev); A.d_o = (const unsigned short *)do_dev; A.delta = delta_dev;
-    A.dq = (unsigned short *)dq_dev; A.dk = (unsigned short *)dk_dev; A.dv = (unsigned short *)dv_dev;
-    A.lddq = lddq; A.lddk = lddk; A.lddv = lddv;
-    A.B = batch; A.S = seq; A.Hq = n_q_heads; A.Hkv = n_kv_heads; A.scale = scale;
-    A.head_splits = 1;
-    set_drop(A, p, seed);
-    rc = check_args(A, head_dim, "ecgb_attn_bwd_dropout");
-    if (rc) return rc;
-    if (lddq % 4 || lddk % 4 || lddv % 4) { ecgb::set_error("ecgb_attn_bwd_dropout: gradient row strides must be multiples of 4"); return ECGB_ERR_UNSUPPORTED; }
-    const unsigned nblk = (unsigned)((seq + 127) / 128);
-    rc = launch_attn(attn_bwd_dq_kernel<64, true>, dim3(nblk * (unsigned)n_q_heads * (unsigned)batch), dim3(256), 3 * 128 * 64 + 4 * ((seq + 63) & ~63), stream, A,
-                     "attn_bwd_dq_kernel<64, dropout>");
-    if (rc) return rc;
-    return launch_attn(attn_bwd_dkv_kernel<64, 1, 0, true>, dim3(nblk * (unsigned)n_kv_heads * (unsigned)batch), dim3(256), 4 * 128 * 64 + 512, stream, A,
-                       "attn_bwd_dkv_kernel<64, dropout>");
+    const char *who = "ecgb_attn_bwd_dropout";
+    if (int rc = check_ptrs(who, {q_dev, k_dev, v_dev, attn_mask_dev, o_dev, lse_dev, do_dev, delta_dev, dq_dev, dk_dev, dv_dev})) return rc;
+    if (int rc = check_drop(p, head_dim, who)) return rc;
+    return attn_bwd_impl(who, q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, do_dev, ldo, lse_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv,
+                         batch, seq, n_q_heads, n_kv_heads, head_dim, scale, scratch_dev, scratch_bytes, stream, nullptr, nullptr, p, seed);
 }
 
 // ecgb_attn_bwd followed by RoPE's backward on dQ and dK (ecgb_rope, inverse), in the attention kernels' own stores: q and k are the ROTATED projections the forward
@@ -1958,13 +1985,42 @@ extern "C" int ecgb_attn_bwd_rope(const void *q_dev, long long ldq, const void *
                                   void *dv_dev, long long lddv, const float *rope_cos_dev, const float *rope_sin_dev, int batch, int seq, int n_q_heads,
                                   int n_kv_heads, int head_dim, float scale, void *scratch_dev, size_t scratch_bytes, void *stream)
 {
-    if (!rope_cos_dev || !rope_sin_dev) { ecgb::set_error("ecgb_attn_bwd_rope: NULL table"); return ECGB_ERR_INVALID; }
-    if (head_dim != 64 || (g_attn_dma & 0x703) != 2 || (lddq & 7) || (lddk & 7) || (((uintptr_t)dq_dev | (uintptr_t)dk_dev | (uintptr_t)rope_cos_dev | (uintptr_t)rope_sin_dev) & 15)) {
-        ecgb::set_error("ecgb_attn_bwd_rope: head_dim 64 on the lean kernels with 16-byte aligned gradient rows only");
-        return ECGB_ERR_UNSUPPORTED;
+    const char *who = "ecgb_attn_bwd_rope";
+    if (int rc = check_ptrs(who, {q_dev, k_dev, v_dev, attn_mask_dev, o_dev, lse_dev, do_dev, delta_dev, dq_dev, dk_dev, dv_dev})) return rc;
+    if (int rc = check_rope(dq_dev, lddq, dk_dev, lddk, rope_cos_dev, rope_sin_dev, head_dim, who)) return rc;
+    return attn_bwd_impl(who, q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, do_dev, ldo, lse_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv,
+                         batch, seq, n_q_heads, n_kv_heads, head_dim, scale, scratch_dev, scratch_bytes, stream, rope_cos_dev, rope_sin_dev, 0.f, 0);
+}
+
+// The plan of a call, for reading without a device: what `entry` (0 ecgb_attn_fwd, 1 ecgb_attn_bwd, 2 ecgb_attn_bwd_rope, 3 ecgb_attn_fwd_dropout, 4 ecgb_attn_bwd_dropout) would
+// launch for these operands under the current switches.  The addresses count for their alignment only; mask, o, lse and delta are taken as given.
+extern "C" int ecgb_attn_launch_plan(int entry, float p, const void *q, long long ldq, const void *k, long long ldk, const void *v, long long ldv, const void *d_o, long long ldo,
+                                     const void *dq, long long lddq, const void *dk, long long lddk, const void *dv, long long lddv, const void *rope_cos, const void *rope_sin,
+                                     int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim, const void *scratch, size_t scratch_bytes,
+                                     int *n_launches, int *grid_block_lds, long long *args_set, char *names, int names_cap)
+{
+    static const char *const kWho[] = {"ecgb_attn_fwd", "ecgb_attn_bwd", "ecgb_attn_bwd_rope", "ecgb_attn_fwd_dropout", "ecgb_attn_bwd_dropout"};
+    if (entry < 0 || entry > 4 || !n_launches || !grid_block_lds || !args_set || !names || names_cap <= 0) return refuse("ecgb_attn_launch_plan", "bad arguments", ECGB_ERR_INVALID);
+    const char *who = kWho[entry];
+    const bool fwd = entry == 0 || entry == 3, drop_entry = entry >= 3;
+    if (int rc = fwd ? check_ptrs(who, {q, k, v}) : check_ptrs(who, {q, k, v, d_o, dq, dk, dv})) return rc;
+    if (drop_entry) { if (int rc = check_drop(p, head_dim, who)) return rc; }
+    if (entry == 2) { if (int rc = check_rope(dq, lddq, dk, lddk, rope_cos, rope_sin, head_dim, who)) return rc; }
+    AttnArgs A = attn_args(q, ldq, k, ldk, v, ldv, nullptr, nullptr, ldo, nullptr, batch, seq, n_q_heads, n_kv_heads, 1.f);
+    if (!fwd) attn_args_bwd(A, d_o, nullptr, const_cast<void *>(dq), lddq, const_cast<void *>(dk), lddk, const_cast<void *>(dv), lddv, nullptr, nullptr, nullptr);
+    AttnPlan P;
+    const bool drop = drop_entry && p > 0.f;
+    if (int rc = fwd ? plan_fwd(A, head_dim, drop, who, P) : plan_bwd(A, head_dim, drop, scratch, scratch_bytes, who, P)) return rc;
+    std::string all;
+    for (int i = 0; i < P.n; ++i) {
+        grid_block_lds[3 * i] = (int)P.launch[i].grid; grid_block_lds[3 * i + 1] = (int)P.launch[i].block; grid_block_lds[3 * i + 2] = P.launch[i].lds;
+        all += (i ? "\n" : "") + std::string(P.launch[i].name);
     }
-    return attn_bwd_impl(q_dev, ldq, k_dev, ldk, v_dev, ldv, attn_mask_dev, o_dev, do_dev, ldo, lse_dev, delta_dev, dq_dev, lddq, dk_dev, lddk, dv_dev, lddv,
-                         batch, seq, n_q_heads, n_kv_heads, head_dim, scale, scratch_dev, scratch_bytes, stream, rope_cos_dev, rope_sin_dev);
+    *n_launches = P.n;
+    args_set[0] = P.lean_hw_log2; args_set[1] = P.head_splits;
+    args_set[2] = P.pbuf ? (long long)(reinterpret_cast<const unsigned char *>(P.pbuf) - static_cast<const unsigned char *>(scratch)) : -1;
+    snprintf(names, (size_t)names_cap, "%s", all.c_str());
+    return ECGB_OK;
 }
 
 #ifdef ECGB_PROFILE

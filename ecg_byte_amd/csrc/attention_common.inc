@@ -38,11 +38,14 @@ struct AttnArgs {
     unsigned drop_thr = 0;
     float drop_inv = 1.f;
 };
-// attention_d256.hip (round 6): the head_dim-256 backward kernels whose LDS reads the compiler schedules.  Each sets the dynamic-LDS attribute, launches and reports like
-// launch_attn(); `seq` sizes the key mask in LDS.
-int launch_bwd_dq_d256(const AttnArgs &A, unsigned grid, int seq, void *stream);
-int launch_bwd_dkv_pair_d256(const AttnArgs &A, unsigned grid, void *stream);
-int launch_bwd_dk_then_dv_d256(const AttnArgs &A, unsigned grid_each, void *stream);      // (A.pbuf set: the dK pass with its P stores, then the dV kernel that reads them)
+// One launch of a plan (attention.hip: plan_fwd / plan_bwd): the kernel, its name for error texts, 1-D grid and block, bytes of dynamic LDS
+using AttnKern = void (*)(AttnArgs);
+struct AttnLaunch { AttnKern kern; const char *name; unsigned grid, block; int lds; };
+// attention_d256.hip (round 6): the head_dim-256 backward kernels whose LDS reads the compiler schedules, as plan entries with their dynamic LDS
+AttnLaunch bwd_dq_d256(unsigned grid, int seq);
+AttnLaunch bwd_dkv_pair_d256(unsigned grid);
+AttnLaunch bwd_dk_d256(unsigned grid);          // (A.pbuf set: the dK pass with its P stores ...
+AttnLaunch bwd_dv_d256(unsigned grid);          //  ... then the dV kernel that reads them)
 }  // namespace ecgb_attn
 
 namespace {
@@ -67,6 +70,8 @@ __device__ __forceinline__ float max3(float a, float b, float c)
 __device__ __forceinline__ float bf2f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 
 using ecgb_attn::AttnArgs;
+using ecgb_attn::AttnKern;
+using ecgb_attn::AttnLaunch;
 
 // after a launch: ECGB_OK, or the HIP error under the kernel's name
 inline int launched(const char *what)
@@ -76,6 +81,28 @@ inline int launched(const char *what)
     ecgb::set_error(std::string(what) + ": " + hipGetErrorString(e));
     return ECGB_ERR_HIP;
 }
+// One kernel launch: the dynamic-LDS attribute (where the kernel takes any), then the launch; either failure is reported HERE with the kernel's name (a refused
+// attribute used to skip the launch silently and leave it to a later hipGetLastError -- which does not see it: the outputs stayed unwritten, status OK).
+template <typename Args>
+int launch_attn(void (*kern)(Args), const char *name, unsigned grid, unsigned block, int lds, void *stream, const Args &A)
+{
+    if (lds > 0) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) {
+            ecgb::set_error(std::string(name) + ": hipFuncSetAttribute(" + std::to_string(lds) + " bytes of dynamic LDS): " + hipGetErrorString(e));
+            return ECGB_ERR_HIP;
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, (hipStream_t)stream, A);
+    return launched(name);
+}
+
+// ---- dynamic LDS that more than one file sizes ----
+constexpr long long kLdsMax = 160 * 1024;       // a CU's LDS: the most one workgroup may ask for
+// the batch row's key mask as floats, over whole 64-key tiles
+inline long long mask_lds_bytes(int seq) { return 4 * (((long long)seq + 63) & ~63ll); }
+// head_dim 256 LDS-DMA kernels (attn_fwd_d256_kernel, attn_bwd_dq_d256_kernel): the two-stage ring of (K, V) tiles of 64 rows x 512 bytes, the key mask, 64 tile flags
+inline long long ring256_lds_bytes(int seq) { return 4 * 64 * 512 + mask_lds_bytes(seq) + 256; }
 
 #ifdef ECGB_PROFILE
 // dev builds only (`make prof`, scripts/dev_prof_attn.py): cycles per phase of the forward loop, summed over waves

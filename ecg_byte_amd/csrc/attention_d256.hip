@@ -664,25 +664,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_pair_d256_kernel(AttnArgs
     else attn_bwd_dkv_d256_body<1>(A, kblk, group / A.Hkv, group % A.Hkv, hsplit);
 }
 
-int launched256(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return ECGB_OK;
-    ecgb::set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return ECGB_ERR_HIP;
-}
-template <typename Kern>
-int launch256(Kern kern, unsigned grid, int lds, void *stream, const AttnArgs &A, const char *what)
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-        ecgb::set_error(std::string(what) + ": hipFuncSetAttribute(" + std::to_string(lds) + " bytes of dynamic LDS): " + hipGetErrorString(e));
-        return ECGB_ERR_HIP;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, (hipStream_t)stream, A);
-    return launched256(what);
-}
-
 }  // namespace
 
 #ifdef ECGB_PROFILE
@@ -695,19 +676,11 @@ extern "C" void ecgb_debug_attn256_profile(unsigned long long *out64, int reset)
 #endif
 
 namespace ecgb_attn {
-// dynamic LDS: the two-stage ring, the row's key mask, the tile flags
-int launch_bwd_dq_d256(const AttnArgs &A, unsigned grid, int seq, void *stream)
-{
-    return launch256(attn_bwd_dq_d256_kernel, grid, 4 * 64 * 512 + 4 * ((seq + 63) & ~63) + 256, stream, A, "attn_bwd_dq_d256_kernel");
-}
-int launch_bwd_dk_then_dv_d256(const AttnArgs &A, unsigned grid_each, void *stream)
-{
-    const int rc = launch256(attn_bwd_dk_d256_kernel, grid_each, 2 * (2 * 64 * 512 + 512), stream, A, "attn_bwd_dk_d256_kernel");
-    if (rc) return rc;
-    return launch256(attn_bwd_dv_d256_kernel, grid_each, 2 * 64 * 512, stream, A, "attn_bwd_dv_d256_kernel");
-}
-int launch_bwd_dkv_pair_d256(const AttnArgs &A, unsigned grid, void *stream)
-{
-    return launch256(attn_bwd_dkv_pair_d256_kernel, grid, 2 * (2 * 64 * 512 + 512), stream, A, "attn_bwd_dkv_pair_d256_kernel");
-}
+// the kernels above as plan entries (attention.hip: plan_bwd), each with its dynamic LDS: the dQ ring (ring256_lds_bytes); for the dK pass, alone or in the pair kernel,
+// two stages of (Q, dO) tiles of 64 rows x 512 bytes + 512 bytes of statistics; for the dV kernel two dO tiles
+constexpr int kDkPassLds = 2 * (2 * 64 * 512 + 512);
+AttnLaunch bwd_dq_d256(unsigned grid, int seq) { return {attn_bwd_dq_d256_kernel, "attn_bwd_dq_d256_kernel", grid, 256, (int)ring256_lds_bytes(seq)}; }
+AttnLaunch bwd_dkv_pair_d256(unsigned grid) { return {attn_bwd_dkv_pair_d256_kernel, "attn_bwd_dkv_pair_d256_kernel", grid, 256, kDkPassLds}; }
+AttnLaunch bwd_dk_d256(unsigned grid) { return {attn_bwd_dk_d256_kernel, "attn_bwd_dk_d256_kernel", grid, 256, kDkPassLds}; }
+AttnLaunch bwd_dv_d256(unsigned grid) { return {attn_bwd_dv_d256_kernel, "attn_bwd_dv_d256_kernel", grid, 256, 2 * 64 * 512}; }
 }  // namespace ecgb_attn

@@ -9,22 +9,16 @@
 //     (16-byte stores where S % 8 == 0; 4- or 2-byte stores where rows are not 16-byte aligned, e.g. S = 2050);
 //   * sum form (fp32 [B, S, S]): the heads are added in fp32 registers in ascending order and stored once (32 lanes = 128 contiguous bytes a row), so every
 //     launch gives the same bits, with or without the full form beside it.
-// Nothing here is shared with the training kernels: attention.hip / attention_d256.hip are untouched.
-#include <hip/hip_runtime.h>
-
+// No device code is shared with the training kernels (attention.hip / attention_d256.hip); the launch helper is (attention_common.inc).
 #include <cmath>
-#include <string>
 
-#include "tokenizer.hpp"
+#include "attention_common.inc"
 #include "../../include/ecgbyte_decoder.h"
 
 namespace {
 
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kTile = 64;
 constexpr int kLdsRow = kTile + 8;     // bf16 elements a staged row: 144 bytes (16-byte aligned, the two wave halves' rows 4 apart land on different banks)
 
@@ -154,13 +148,9 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(ProbsArgs A)
 template <int D>
 int launch_probs(const ProbsArgs &A, unsigned grid, void *stream)
 {
-    if (A.S % 8 == 0) hipLaunchKernelGGL((attn_probs_kernel<D, 8>), dim3(grid), dim3(256), 0, (hipStream_t)stream, A);
-    else if (A.S % 2 == 0) hipLaunchKernelGGL((attn_probs_kernel<D, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL((attn_probs_kernel<D, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, A);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return ECGB_OK;
-    ecgb::set_error(std::string("attn_probs_kernel: ") + hipGetErrorString(e));
-    return ECGB_ERR_HIP;
+    void (*kern)(ProbsArgs) = attn_probs_kernel<D, 8>;
+    if (A.S % 8) kern = A.S % 2 == 0 ? attn_probs_kernel<D, 2> : attn_probs_kernel<D, 1>;
+    return launch_attn(kern, "attn_probs_kernel", grid, 256, 0, stream, A);
 }
 
 }  // namespace

@@ -816,19 +816,23 @@ def _off(t, off):
     return C.c_void_p(t.data_ptr() + off * t.element_size())
 
 
+def _qkv(t, Hq, Hkv, D):
+    """The q | k | v operands of a fused buffer [B*S, Hq*D + 2*Hkv*D] as the attention entry points take them: (q, ld, k, ld, v, ld)."""
+    ld = t.shape[1]
+    return _off(t, 0), ld, _off(t, Hq * D), ld, _off(t, Hq * D + Hkv * D), ld
+
+
 def attn_fwd(qkv, mask, B, S, Hq, Hkv, D, scale, drop=None):
     """Fused attention on a fused qkv buffer [B*S, Hq*D + 2*Hkv*D] (q | k | v).  Returns (o [B*S, Hq*D], lse).
     drop = (p, seed): inverted dropout on the probabilities inside the kernel (ecgb_attn_fwd_dropout: head_dim 64; the mask ops.dropout draws on a
     contiguous [B*Hq, S, S] tensor from the same (p, seed)); lse is that of the undropped probabilities.  Hand the same `drop` to attn_bwd."""
-    QKV = qkv.shape[1]
     o = torch.empty((B * S, Hq * D), dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty((B, Hq, S), dtype=torch.float32, device=qkv.device)
+    qkv_ops = _qkv(qkv, Hq, Hkv, D)
     if drop is not None:
-        _lib.check(_L().ecgb_attn_fwd_dropout(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _off(qkv, Hq * D + Hkv * D), QKV, _p(mask),
-                                              _p(o), Hq * D, _p(lse), B, S, Hq, Hkv, D, float(scale), float(drop[0]), int(drop[1]), _st()))
+        _lib.check(_L().ecgb_attn_fwd_dropout(*qkv_ops, _p(mask), _p(o), Hq * D, _p(lse), B, S, Hq, Hkv, D, float(scale), float(drop[0]), int(drop[1]), _st()))
         return o, lse
-    _lib.check(_L().ecgb_attn_fwd(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _off(qkv, Hq * D + Hkv * D), QKV, _p(mask),
-                                  _p(o), Hq * D, _p(lse), B, S, Hq, Hkv, D, float(scale), _st()))
+    _lib.check(_L().ecgb_attn_fwd(*qkv_ops, _p(mask), _p(o), Hq * D, _p(lse), B, S, Hq, Hkv, D, float(scale), _st()))
     return o, lse
 
 
@@ -842,8 +846,7 @@ def attn_probs(qkv, mask, lse, B, S, Hq, Hkv, D, scale, probs=None, psum=None, w
     if psum is not None:
         assert psum.dtype == torch.float32 and psum.is_contiguous() and psum.shape == (B, S, S)
     assert lse.dtype == torch.float32 and lse.is_contiguous() and lse.shape == (B, Hq, S)
-    QKV = qkv.shape[1]
-    _lib.check(_L().ecgb_attn_probs(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _p(mask), _p(lse), _p(probs), _p(psum), float(weight),
+    _lib.check(_L().ecgb_attn_probs(*_qkv(qkv, Hq, Hkv, D)[:4], _p(mask), _p(lse), _p(probs), _p(psum), float(weight),
                                     int(bool(accumulate)), B, S, Hq, Hkv, D, float(scale), _st()))
     return probs, psum
 
@@ -915,26 +918,22 @@ def attn_bwd(qkv, mask, o, do, lse, B, S, Hq, Hkv, D, scale, rope=None, drop=Non
     delta = torch.empty((B, Hq, S), dtype=torch.float32, device=qkv.device)
     nbytes = _L().ecgb_attn_bwd_scratch_bytes(B, S, Hq, Hkv, D)          # head_dim 256: partial dK / dV slabs (few key blocks) + the probabilities from the dK pass to the dV kernel; else 0
     scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=qkv.device) if nbytes else None
+    # q | k | v, mask, o, dO, lse, delta, dq | dk | dv: what every backward entry point starts with; shape, scale and scratch: what follows
+    ops = (*_qkv(qkv, Hq, Hkv, D), _p(mask), _p(o), _p(_bf(do)), Hq * D, _p(lse), _p(delta), *_qkv(d_qkv, Hq, Hkv, D))
+    rest = (B, S, Hq, Hkv, D, float(scale), _p(scratch), nbytes)
     if drop is not None:
-        _lib.check(_L().ecgb_attn_bwd_dropout(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _off(qkv, Hq * D + Hkv * D), QKV, _p(mask),
-                                              _p(o), _p(_bf(do)), Hq * D, _p(lse), _p(delta), _off(d_qkv, 0), QKV, _off(d_qkv, Hq * D), QKV,
-                                              _off(d_qkv, Hq * D + Hkv * D), QKV, B, S, Hq, Hkv, D, float(scale), _p(scratch), nbytes,
-                                              float(drop[0]), int(drop[1]), _st()))
+        _lib.check(_L().ecgb_attn_bwd_dropout(*ops, *rest, float(drop[0]), int(drop[1]), _st()))
         if rope is not None:
             rope_(d_qkv, rope[0], rope[1], Hq + Hkv, D, QKV, inverse=True)
         return d_qkv
     if rope is not None and _fuse_rope_bwd and D == 64:
         cos, sin = rope
-        rc = _L().ecgb_attn_bwd_rope(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _off(qkv, Hq * D + Hkv * D), QKV, _p(mask),
-                                     _p(o), _p(_bf(do)), Hq * D, _p(lse), _p(delta), _off(d_qkv, 0), QKV, _off(d_qkv, Hq * D), QKV,
-                                     _off(d_qkv, Hq * D + Hkv * D), QKV, _p(cos), _p(sin), B, S, Hq, Hkv, D, float(scale), _p(scratch), nbytes, _st())
+        rc = _L().ecgb_attn_bwd_rope(*ops, _p(cos), _p(sin), *rest, _st())
         if rc == 0:
             return d_qkv
         if rc != -3:                                                     # ECGB_ERR_UNSUPPORTED: the two steps apart, below
             _lib.check(rc)
-    _lib.check(_L().ecgb_attn_bwd(_off(qkv, 0), QKV, _off(qkv, Hq * D), QKV, _off(qkv, Hq * D + Hkv * D), QKV, _p(mask),
-                                  _p(o), _p(_bf(do)), Hq * D, _p(lse), _p(delta), _off(d_qkv, 0), QKV, _off(d_qkv, Hq * D), QKV,
-                                  _off(d_qkv, Hq * D + Hkv * D), QKV, B, S, Hq, Hkv, D, float(scale), _p(scratch), nbytes, _st()))
+    _lib.check(_L().ecgb_attn_bwd(*ops, *rest, _st()))
     if rope is not None:
         rope_(d_qkv, rope[0], rope[1], Hq + Hkv, D, QKV, inverse=True)
     return d_qkv

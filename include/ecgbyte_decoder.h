@@ -271,7 +271,8 @@ int ecgb_softmax_bwd(const void *p_dev, void *dp_dev, int batch_heads, int seq, 
  * Key j is visible to query i iff j <= i and attn_mask[b, j] != 0; rows without a visible key give zeros.
  * lse_dev [batch, n_q_heads, seq] fp32 is saved for the backward.  head_dim 64 (Llama, GPT-2), 128 or 256 (Gemma).
  * The row's key mask lives in LDS: seq at most 28 608 (head_dim 64), 24 576 (128) or 8 192 (256); longer is ECGB_ERR_UNSUPPORTED
- * before any launch (ecgb_attn_bwd likewise). */
+ * before any launch (ecgb_attn_bwd likewise).  A null q, k, v, mask, o or lse (ecgb_attn_bwd and its forms: or dO, delta, dq, dk, dv) is
+ * ECGB_ERR_INVALID before anything else; every message starts with the name of the entry point that was called. */
 int ecgb_attn_fwd(const void *q_dev, long long ldq, const void *k_dev, long long ldk, const void *v_dev, long long ldv,
                   const float *attn_mask_dev, void *o_dev, long long ldo, float *lse_dev, int batch, int seq,
                   int n_q_heads, int n_kv_heads, int head_dim, float scale, void *stream);
@@ -344,6 +345,16 @@ int ecgb_attn_bwd_dropout(const void *q_dev, long long ldq, const void *k_dev, l
                           float *delta_dev, void *dq_dev, long long lddq, void *dk_dev, long long lddk, void *dv_dev,
                           long long lddv, int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim, float scale, void *scratch_dev, size_t scratch_bytes,
                           float p, uint64_t seed, void *stream);
+/* What a call of `entry` (0 ecgb_attn_fwd, 1 ecgb_attn_bwd, 2 ecgb_attn_bwd_rope, 3 ecgb_attn_fwd_dropout, 4 ecgb_attn_bwd_dropout; p counts for 3 and 4, the
+ * gradient operands for 1, 2 and 4, the tables for 2) with these operands would launch under the current switches, decided by the code that launches -- and no
+ * device touched, so tests can read it anywhere.  The addresses count for their alignment only; mask, o, lse and delta are taken as given.  Returns what the
+ * entry point would return before its first launch, with the same ecgb_last_error().  On ECGB_OK: *n_launches (at most 4); grid_block_lds[3 i .. 3 i + 2] =
+ * workgroups, threads a workgroup and bytes of dynamic LDS of launch i; the kernels' names in `names`, one a line (cut at names_cap);
+ * args_set = {AttnArgs::lean_hw_log2, head_splits, byte offset of pbuf inside the scratch or -1}. */
+int ecgb_attn_launch_plan(int entry, float p, const void *q, long long ldq, const void *k, long long ldk, const void *v, long long ldv, const void *d_o, long long ldo,
+                          const void *dq, long long lddq, const void *dk, long long lddk, const void *dv, long long lddv, const void *rope_cos, const void *rope_sin,
+                          int batch, int seq, int n_q_heads, int n_kv_heads, int head_dim, const void *scratch, size_t scratch_bytes,
+                          int *n_launches, int *grid_block_lds, long long *args_set, char *names, int names_cap);
 
 /* One decode step of generate(): q [batch, n_q_heads*head_dim] against a KV cache whose rows (one per position) are
  * `ld` elements apart, `capacity` rows per batch entry, KV head g at + g*head_dim; the first kv_len rows are valid
